@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the unrolled-GLAD hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one training pass of the hot path over one batch of synthetic covariances already resident in HBM:
 forward_uGLAD (Theta_0 init, L GLAD cells, glasso loss) + backward + gradient exchange + Adam.  Workload per GPU =
 BASELINE.json config 3: M=1024 matrices, D=128, L=30, fp32; with N GPUs every rank holds its own 1024 (weak scaling,
 global batch 1024*N = config 4 at N=8) and the per-step lambda scalar + the 43-float gradient message go over RCCL.
-metric value = M_global * L * K / wall time (unroll-steps per second, whole job).
+metric value = M_global * L * K / wall time (unroll-steps per second, whole job); ms_per_step = wall time / K.
 
-The JSON line also carries:
+A plain run sets up, warms up, times the K steps, writes its outputs if asked and prints the JSON line, nothing more.
+--dump-outputs DIR writes what the last timed step returned to its caller, as DIR/<name>.npy (rank 0): a fixed, seeded sample of
+Theta_L's matrices (theta_sample, their batch indices in theta_sample_index), the loss, the parameters after the Adam step
+(param.<name>) and their gradients (grad.<name>).  The inputs are seeded, so two builds can be compared output for output.
+
+--full adds what the headline figure does not need; the JSON line then also carries:
+  forward_only_steps_per_s  the same workload as no_grad forward passes (the predict / CV-final path);
   roofline      the dominant kernel's ALGORITHMIC flops per launch (forward 20/3 D^3 + 50 D^2, backward
                 8 D^3 + 100 D^2 per matrix) / its mean launch duration measured here with HIP events, against the f32 MFMA peak;
   cpu_baseline  the oracle's NS-faithful CPU restatement of the reference (oracle/glad_ns.py) timed on this host's cores on a
@@ -114,6 +120,23 @@ def _baseline_config(M, D, L):
     return "not a BASELINE configuration"
 
 
+def _dump_outputs(out_dir, theta, loss, model):
+    """The last timed step's outputs as <name>.npy: Theta_L of a seeded sample of the batch (<= 64 matrices, <= 32 MiB), loss,
+    parameters after the optimizer step and their gradients."""
+    os.makedirs(out_dir, exist_ok=True)
+    M, D = theta.shape[0], theta.shape[-1]
+    k = max(1, min(M, 64, (32 << 20) // (D * D * 4)))
+    idx = np.sort(np.random.default_rng(0).choice(M, size=k, replace=False))
+    arrays = {"theta_sample": theta[torch.from_numpy(idx).to(theta.device)].float().cpu().numpy(),
+              "theta_sample_index": idx.astype(np.float64), "loss": loss.detach().float().cpu().numpy()}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    _log(f"wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB) to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -123,13 +146,18 @@ def main():
     ap.add_argument("--D", type=int, default=128)
     ap.add_argument("--L", type=int, default=30)
     ap.add_argument("--sqrt-mode", default="ns10")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the forward-only rate, the roofline of the dominant kernels and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--phase", default="all", choices=("all", "train", "infer"),
                     help="counter collection only (scripts/gpu_pmc.sh): run just the training steps or just the forward-only passes, so that "
                          "per-launch HBM traffic can be reported per flavour (a training launch also writes U and theta_half); no JSON line")
     ap.add_argument("--cpu-sample", type=int, default=32, help="matrices in the CPU baseline sub-batch")
     ap.add_argument("--cpu-passes", type=int, default=6, help="timed CPU passes (plus one untimed)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -193,7 +221,7 @@ def main():
         loss.backward()
         um._allreduce_grads(model, loss, coll)
         opt.step()
-        return loss
+        return theta.detach(), loss
 
     def barrier():
         if world > 1:
@@ -213,7 +241,7 @@ def main():
         _log("warm-up done")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = train_step()
+        theta, loss = train_step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -224,24 +252,28 @@ def main():
     final_loss = float(loss.item())
     if rank == 0:
         _log(f"timed {args.steps} training steps: {dt / args.steps * 1e3:.1f} ms/step, {value:.0f} unroll-steps/s")
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, theta, loss, model)
     if args.phase == "train":  # (counter collection: training launches alone)
         return
 
-    # ---- forward-only rate (no_grad: the predict / CV-final path)
-    with torch.no_grad():
-        um.forward_uGLAD(S, model, L=L, sqrt_mode=args.sqrt_mode, collective=coll, global_batch=Mg)
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(max(1, args.steps)):
+    # ---- forward-only rate (no_grad: the predict / CV-final path); this and everything below up to the JSON line: --full only
+    fwd_rate = None
+    if args.full:
+        with torch.no_grad():
             um.forward_uGLAD(S, model, L=L, sqrt_mode=args.sqrt_mode, collective=coll, global_batch=Mg)
-        barrier()
-        fwd_rate = Mg * L * max(1, args.steps) / (time.perf_counter() - t0)
-    if rank == 0:
-        _log(f"forward-only: {fwd_rate:.0f} unroll-steps/s")
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(max(1, args.steps)):
+                um.forward_uGLAD(S, model, L=L, sqrt_mode=args.sqrt_mode, collective=coll, global_batch=Mg)
+            barrier()
+            fwd_rate = Mg * L * max(1, args.steps) / (time.perf_counter() - t0)
+        if rank == 0:
+            _log(f"forward-only: {fwd_rate:.0f} unroll-steps/s")
 
     # ---- roofline of the dominant kernels: HIP events on the launch stream around single launches
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         mode = _lib.SQRT_MODES[args.sqrt_mode]
         f32 = dict(dtype=torch.float32, device=dev)
         pk = model.packed().detach().contiguous()
@@ -335,7 +367,7 @@ def main():
 
     # ---- CPU baseline: the oracle's NS-faithful restatement of the reference on a bounded sub-batch (rank 0, N=1)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import glad_ns as ns
 
         _log(f"roofline: {roof}")
@@ -397,12 +429,11 @@ def main():
             "config": {"workload": f"multi-task M={M}/GPU D={D} L={L} fp32 ({_baseline_config(M, D, L)}; global batch {Mg})",
                        "pass": "training step: forward + loss + backward + gradient exchange + Adam",
                        "sqrt_mode": args.sqrt_mode, "parallelism": f"batch-sharded x{world}", "per_step_exchange": exchange},
-            "forward_only_steps_per_s": round(fwd_rate, 1),
             "final_loss": final_loss,
             "input_gen_s": round(gen_s, 1),
-            "roofline": roof,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update(forward_only_steps_per_s=round(fwd_rate, 1), roofline=roof, cpu_baseline=cpu)
         if rccl is not None:
             out["rccl"] = rccl
         print(json.dumps(out), flush=True)

@@ -13,6 +13,6 @@ for l in sys.stdin:
         d=json.loads(l); r=d["roofline"]
         print(sys.argv[1], "ms/step", d["ms_per_step"], "fwd-only steps/s", d["forward_only_steps_per_s"], " ".join(f"{k}={v['"'"'launch_ms'"'"']}" for k,v in r["other"].items()), "fwd_cell", r["forward_cell"]["launch_ms"])'
 for i in $(seq 1 $N); do
-  UGLAD_LIB=$PWD/$A timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" "A($A)" | tee -a $OUT || exit 1
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" "B(in-tree)" | tee -a $OUT || exit 1
+  UGLAD_LIB=$PWD/$A timeout -k 10 300 python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" "A($A)" | tee -a $OUT || exit 1
+  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" "B(in-tree)" | tee -a $OUT || exit 1
 done

@@ -9,8 +9,8 @@ export TMPDIR=/tmp
 export UGLAD_BENCH_NOFORK=1  # no forked input generation under rocprofv3 (its preloaded library initialises the GPU first)
 O=gpurun_out/evidence; rm -rf $O; mkdir -p $O
 run() { local name=$1 to=$2; shift 2; echo "=== $name"; timeout -k 10 "$to" "$@" > $O/$name.log 2>&1; local rc=$?; echo "=== $name rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 90; fi; }
-run bench 400 python bench.py --steps 20 --warmup 5
-run bench_m8192 300 python bench.py --M 8192 --steps 3 --warmup 1 --no-cpu-baseline
+run bench 400 python bench.py --steps 20 --warmup 5 --full
+run bench_m8192 300 python bench.py --M 8192 --steps 3 --warmup 1 --full --no-cpu-baseline
 rm -rf gpurun_out/prof
 run rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline
 find gpurun_out/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \; 2>/dev/null

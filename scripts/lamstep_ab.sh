@@ -17,8 +17,8 @@ else
   for cfg in "1024 128 30" "128 64 30"; do
     set -- $cfg
     for r in 1 2 3; do
-      timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 in the cell     " || exit 90
-      UGLAD_NO_FUSED_LAMBDA=1 timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 launch of its own" || exit 90
+      timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 in the cell     " || exit 90
+      UGLAD_NO_FUSED_LAMBDA=1 timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 launch of its own" || exit 90
     done
   done
 fi

@@ -15,7 +15,7 @@ for cfg in "1 25 15" "128 64 30" "8 32 15" "2048 64 10" "4096 32 10" "1024 48 10
   set -- $cfg
   for i in 1 2; do
     for mode in 1 0; do
-      UGLAD_TRIDIAG_WAVE=$mode timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 wave=$mode" | tee -a $OUT || exit 1
+      UGLAD_TRIDIAG_WAVE=$mode timeout -k 10 300 python bench.py --M $1 --D $2 --L $3 --steps 10 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "$pick" "M=$1 D=$2 L=$3 wave=$mode" | tee -a $OUT || exit 1
     done
   done
 done
