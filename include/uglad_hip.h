@@ -171,6 +171,13 @@ int uglad_loss_fwd(const float* theta, const float* S, int s_batch, const float*
 int uglad_loss_bwd(const float* theta, const float* theta_inv, const float* S, int s_batch, const float* struct_theta,
                    const float* g_up, float scale, float* G_out, int M, int D, uglad_stream_t stream);
 
+/* uglad_loss_bwd that also OVERWRITES gS (s_batch, D, D) with dL/dS, symmetric part (the convention of uglad_glad_backward_wrt_s):
+ *   gS_b = g_up[0] * scale * sum over the matrices m that read S_b of (Theta_m + Theta_m^T) / 2
+ * -- with s_batch == 1 the sum runs over all M matrices (one S broadcast against the batch).  The structure term does not depend on S.
+ * G_out is bit-identical to uglad_loss_bwd's. */
+int uglad_loss_bwd_wrt_s(const float* theta, const float* theta_inv, const float* S, int s_batch, const float* struct_theta,
+                         const float* g_up, float scale, float* G_out, float* gS, int M, int D, uglad_stream_t stream);
+
 /* Finish the 42 parameter gradients of one backward pass (sums over the LOCAL batch; the caller all-reduces them):
  *   grad[0]      = sum_m gt_partial[m]
  *   grad[1..28]  = sum_m grad_rho_partial[m][:]
@@ -208,6 +215,23 @@ int uglad_glad_backward_grouped(const float* G_L, const float* S, const float* p
                                 const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
                                 float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
                                 float* grad, float* workspace, int M, int D, int groups, int sqrt_mode, uglad_stream_t stream);
+
+/* The gradient with respect to the input covariance.  uglad_glad_backward_grouped (groups == 1: the plain pass) that also OVERWRITES
+ * gS (M,D,D) with dL/dS of the whole pass:
+ *   sum over the steps k of  G_B,k / lambda_k  (b_k = S / lambda_k - Z_k, glad.py:139)  +  the rhoNN input gradient of the S feature
+ *   (glad.py:144, glad_params.py:75)  +  the Theta_0 term: -Theta_0 G_0 Theta_0 (init_diag 0) or -G_0,ii Theta_0,ii^2 (init_diag 1).
+ * lambda_k contributes nothing: LambdaNN's inputs are detached (glad_params.py:94).
+ * Convention: gS is the SYMMETRIC part (G + G^T) / 2 of the gradient autograd forms for the reference, which treats the D^2 entries of S
+ * as independent; gS is exactly symmetric.  Every symmetric parametrisation of S (S = Xc^T Xc / N, ...) sees the same upstream gradient.
+ * Theta, the 42 parameter gradients and G_0 come out bit-identical to uglad_glad_backward_grouped's (gbuf0/gbuf1 are scratch).
+ * Kernels: on the spectral path's one-workgroup backward a variant of the cell kernel forms the step's terms (all L steps in one launch
+ * for D <= 128); on the many-workgroups backward (uglad_set_wide_mode) and the matrix-iteration path (D > uglad_max_eig_dim(), or
+ * uglad_set_matrix_iteration) the step runs unchanged and one elementwise kernel behind it forms them again from G_next, G_out and the
+ * saved state (gz - sym(G_out) = G_B).  The Theta_0 term beyond the one-workgroup kernels: two tiled fp32 products. */
+int uglad_glad_backward_wrt_s(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
+                              const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
+                              float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
+                              float* grad, float* workspace, int M, int D, int groups, int sqrt_mode, float* gS, uglad_stream_t stream);
 
 /* The unrolled pass of ONE RANK of a batch-sharded run, enqueued by one call (collective site i: the batch mean
  * behind get_frobenius_norm, glad.py:60-71,147, is the only coupling between the matrices of a batch).  As uglad_glad_forward on the M

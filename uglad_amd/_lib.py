@@ -66,6 +66,10 @@ _SIGS = {
     "uglad_support_metrics": ([_c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
                               ctypes.c_int),
     "uglad_set_wide_mode": ([ctypes.c_int], ctypes.c_int),
+    "uglad_glad_backward_wrt_s": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + [_c_float_p] * 13
+                                  + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_loss_bwd_wrt_s": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_float, _c_float_p,
+                              _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -195,6 +199,12 @@ class HipLib:
         self._call("uglad_loss_bwd", self._p(theta), self._p(theta_inv), self._p(S), S.shape[0], self._p(struct),
                    self._p(g_up), float(scale), self._p(G_out), M, D)
 
+    def loss_bwd_wrt_s(self, theta, theta_inv, S, struct, g_up, scale, G_out, gS):
+        """loss_bwd that also overwrites gS (S's shape) with dL/dS, symmetric part (include/uglad_hip.h)."""
+        M, D, _ = theta.shape
+        self._call("uglad_loss_bwd_wrt_s", self._p(theta), self._p(theta_inv), self._p(S), S.shape[0], self._p(struct),
+                   self._p(g_up), float(scale), self._p(G_out), self._p(gS), M, D)
+
     def finish_grads(self, gt_partial, grad_rho_partial, glam_partial, lam_in, params, grad, L, M):
         self._call("uglad_finish_grads", self._p(gt_partial), self._p(grad_rho_partial), self._p(glam_partial),
                    self._p(lam_in), self._p(params), self._p(grad), int(L), int(M))
@@ -250,12 +260,15 @@ class HipLib:
         return ctypes.cast(self._dll.uglad_rccl_allreduce_sum, ctypes.c_void_p), int(comm)
 
     def glad_backward(self, G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial,
-                      glam_partial, gt_partial, grad, workspace, mode, groups: int = 1):
+                      glam_partial, gt_partial, grad, workspace, mode, groups: int = 1, gS=None):
+        """gS (M,D,D) or None: when given, also dL/dS of the pass (uglad_glad_backward_wrt_s), overwritten."""
         M, D, _ = S.shape
         args = (self._p(G_L), self._p(S), self._p(params), int(init_diag), int(L), self._p(Z), self._p(half), self._p(U),
                 self._p(beta), self._p(lam), self._p(lam_in), self._p(gbuf0), self._p(gbuf1), self._p(grad_rho_partial),
                 self._p(glam_partial), self._p(gt_partial), self._p(grad), self._p(workspace), M, D)
-        if groups == 1:
+        if gS is not None:
+            self._call("uglad_glad_backward_wrt_s", *args, int(groups), int(mode), self._p(gS))
+        elif groups == 1:
             self._call("uglad_glad_backward", *args, int(mode))
         else:
             self._call("uglad_glad_backward_grouped", *args, int(groups), int(mode))

@@ -1,0 +1,416 @@
+// Body of the cell backward kernel, included twice by glad_kernels.hip (inside namespace uglad, per-NT units):
+//   UGLAD_CELL_BWD_GS 0: cell_bwd_kernel     -- the 42 parameter gradients and dL/dZ_k;
+//   UGLAD_CELL_BWD_GS 1: cell_bwd_gs_kernel  -- the same, and also dL/dS of every step accumulated into gS (M, D, D), which the caller zeroed
+//                        before the pass: gS += G_B / lam_k (b_k = S / lam_k - Z_k) + the rhoNN input gradient of the S feature.  The thread that
+//                        owns the upper-triangle entry (i, j) adds both terms to gS_ij and mirrors the sum into gS_ji, so gS stays exactly
+//                        symmetric; everything else is computed by the same code.
+// One body for both, switched by the preprocessor rather than a bool template parameter on a __device__ body: called from two kernels,
+// the device function is simplified on its own before it is inlined, and cell_bwd_kernel came out with other register and spill figures
+// (scripts/kernel_meta.py, NT = 2: 177 instead of 181 VGPRs, 51 instead of 9 SGPR spills).  Included textually, cell_bwd_kernel is token
+// for token the kernel it was; the gS instantiations live in translation units of their own (UGLAD_TU_GS), since next to cell_bwd_kernel<3>
+// they moved its SGPR spills from 78 to 80.
+template <int NT>
+__global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
+    const float* __restrict__ Gnext, const float* __restrict__ S, const float* __restrict__ Zin,
+    const float* __restrict__ half, const float* __restrict__ U, const float* __restrict__ beta,
+    const float* __restrict__ lam_ptr, const float* __restrict__ params, float* __restrict__ Gout,
+    float* __restrict__ grad_rho_partial, float* __restrict__ glam_partial, float* __restrict__ gws, int D, int mode,
+#if UGLAD_CELL_BWD_GS
+    int gs, int k_count, int lam_stride, float* __restrict__ gS) {
+#else
+    int gs, int k_count, int lam_stride) {
+#endif
+  constexpr int DP = NT * 32, LD = DP + 1;
+  UGLAD_BIG_BUFFERS(sX, DP * LD, sY, DP * LD, gws)  // U ; G -> G_half -> T -> C o F -> T2
+  __shared__ float s_beta[DP], s_r[DP];
+  __shared__ __attribute__((aligned(16))) float s_a[kNsIters][DP];  // NS10: a_i^(t) ...
+  __shared__ __attribute__((aligned(16))) float s_q[kNsIters][DP];  // ... and its square
+  __shared__ float s_red[8];
+  __shared__ float s_g[kWaves][kNRho + 1];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const size_t base = (size_t)blockIdx.x * D * D;
+  const float* Sm = S + base;
+  const float* Gm = Gnext + base;
+  float* Go = Gout + base;
+  const int grp = blockIdx.x / gs;
+  params += (size_t)grp * kNParam;
+  // k_count consecutive steps k, k-1, ... of the unrolled pass in ONE launch (DP <= 128 only): the pointers name step k, step k - s sits
+  // s slabs (gridDim.x matrices) below.  dL/dZ stays in LDS from one step to the next -- the two big buffers swap roles -- the 28 rhoNN
+  // gradient sums stay in registers, and only the last step writes G_out.  k_count = 1 is the per-step entry point.
+  const size_t step_mdd = (size_t)gridDim.x * D * D, step_md = (size_t)gridDim.x * D;
+  float g[kNRho];
+#pragma unroll
+  for (int q = 0; q < kNRho; ++q) g[q] = 0.f;
+#pragma unroll 1
+  for (int s = 0; s < k_count; ++s) {
+    const bool first = (s == 0), last = (s == k_count - 1);
+    const int tid = opaque_v(threadIdx.x), lane = tid & 63;  // (shadow the outer ones: nothing per-thread is hoisted)
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the tile indices derived from it live in SGPRs)
+    const float* Zm = Zin + base - s * step_mdd;
+    const float* Hm = half + base - s * step_mdd;
+    const float* Um = U + base - s * step_mdd;
+    const float* bm = beta + (size_t)blockIdx.x * D - s * step_md;
+    const float lam = lam_ptr[(long)grp - (long)s * lam_stride];
+    const float c4 = 4.0f / lam, inv_lam2 = 1.0f / (lam * lam);
+
+    KSTAMP(0);
+    // U -> sX, and in the first step G_next -> sY (afterwards G is there already): row-major, coalesced, 8 loads in flight per thread.
+    // The loads are unconditional (a clamped address, the value selected afterwards): with `in ? load : 0` the compiler put every load
+    // behind its own branch and an s_waitcnt vmcnt(0), one round trip after the other (30 k instead of 17 k ticks for this phase).
+    // (Explicit loops, not a helper taking the destination as a pointer: through a pointer parameter the LDS stores become flat stores
+    // that may alias the loads, and the loop serialises completely -- 137 k ticks.)
+    if (first) {  // 16 loads in flight per thread
+      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
+        float u[8], gv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int idx = idx0 + q * kThreads + tid;
+          const int i = idx / DP, k = idx - i * DP;
+          const bool in = (idx < DP * DP) && i < D && k < D;
+          const int at = in ? i * D + k : 0;
+          const float xu = Um[at], xg = Gm[at];
+          u[q] = in ? xu : 0.f;
+          gv[q] = in ? xg : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int idx = idx0 + q * kThreads + tid;
+          if (idx < DP * DP) {
+            const int i = idx / DP, k = idx - i * DP;
+            sX[i * LD + k] = u[q];
+            sY[i * LD + k] = gv[q];
+          }
+        }
+      }
+    } else {
+      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
+        float u[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int idx = idx0 + q * kThreads + tid;
+          const int i = idx / DP, k = idx - i * DP;
+          const bool in = (idx < DP * DP) && i < D && k < D;
+          const float xu = Um[in ? i * D + k : 0];
+          u[q] = in ? xu : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int idx = idx0 + q * kThreads + tid;
+          if (idx < DP * DP) {
+            const int i = idx / DP, k = idx - i * DP;
+            sX[i * LD + k] = u[q];
+          }
+        }
+      }
+    }
+    float a2 = 0.f;
+    if (tid < D) {
+      const float be = bm[tid];
+      const float al = fmaf(be, be, c4);
+      a2 = al * al;
+    }
+    const float nrmA = sqrtf(block_sum(a2, s_red));
+    float r2 = 0.f;
+    if (tid < DP) {
+      float be = 0.f, r = 1.f;
+      if (tid < D) {
+        be = bm[tid];
+        r = sqrt_spectrum(be, c4, nrmA, mode);
+        r2 = r * r;
+      }
+      s_beta[tid] = be;
+      s_r[tid] = r;
+    }
+    const float nrmR = sqrtf(block_sum(r2, s_red));
+    if (mode == UGLAD_SQRT_NS10 && tid < DP) {
+      float a = s_r[tid] / nrmR;
+#pragma unroll
+      for (int it = 0; it < kNsIters; ++it) {
+        s_a[it][tid] = a;
+        s_q[it][tid] = a * a;
+        a = 0.5f * a * (3.f - a * a);
+      }
+    }
+    __syncthreads();
+
+    KSTAMP(1);
+    // ---- phase A: rhoNN + threshold backward on the upper triangle (entry e = tid + kThreads q, as in the forward cell)
+    using TU = Tiles<NT, true>;
+    constexpr int kMaxQ = ((DP / 2) * (DP + 1) + kThreads - 1) / kThreads;
+    constexpr bool kPre = DP <= 128;          // all entries of a thread in registers at once
+    constexpr int kQ = kPre ? kMaxQ : 8;      // entries per thread and pass
+    const int D1 = D + 1, total = ((D + 1) / 2) * D1;
+    const int sp = kThreads / D1, sc = kThreads - sp * D1;
+    const int p0 = tid / D1, c0 = tid - p0 * D1;
+    auto entry = [&](int e, int p, int c) -> int {  // (i << 16) | j of entry (pair p, offset c), -1 when there is none
+      if (e >= total) return -1;
+      if (c < D - p) return (p << 16) | (p + c);
+      const int i = D - 1 - p;
+      return (i == p) ? -1 : ((i << 16) | (i + (c - (D - p))));
+    };
+    auto advance = [&](int& p, int& c) {
+      c += sc;
+      p += sp;
+      if (c >= D1) {
+        c -= D1;
+        ++p;
+      }
+    };
+    float gz[kQ];  // dL/dZ_in, direct part (through rhoNN's third input); DP > 128: parked in G_out's upper triangle instead
+    {
+      int p = p0, c = c0;
+      for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
+        int pk[kQ];
+        float hx[kQ], zz[kQ], gn[kQ], sv[kQ];
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) {
+          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
+          advance(p, c);
+          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+          const bool in = pk[u] >= 0;
+          if (kPre) gz[u] = 0.f;
+          hx[u] = in ? Hm[i * D + j] : 0.f;
+          zz[u] = in ? Zm[i * D + j] : 0.f;
+          sv[u] = in ? Sm[i * D + j] : 0.f;
+          gn[u] = in ? ((i == j) ? sY[i * LD + j] : 0.5f * (sY[i * LD + j] + sY[j * LD + i])) : 0.f;
+        }
+        // forward activations of two entries at a time on the packed fp32 pipe, the backward entry by entry (packed, its 28
+        // accumulators would need a second set of registers that the kernel does not have)
+        constexpr int kQ2 = (kQ + 1) / 2;
+#pragma unroll
+        for (int h = 0; h < kQ2; ++h) {
+          const int u0 = 2 * h, u1 = (2 * h + 1 < kQ) ? 2 * h + 1 : 2 * h;
+          const bool has1 = 2 * h + 1 < kQ;
+          if (!has1 && pk[u0] < 0) continue;  // (the odd one out exists on a few threads only)
+          RhoAct2 act2;
+          rho_forward2(params, (v2f){hx[u0], has1 ? hx[u1] : 0.f}, (v2f){sv[u0], has1 ? sv[u1] : 0.f},
+                       (v2f){zz[u0], has1 ? zz[u1] : 0.f}, act2);
+#pragma unroll
+          for (int c2 = 0; c2 < 2; ++c2) {
+            const int u = c2 ? u1 : u0;
+            if ((c2 == 0 || has1) && pk[u] >= 0) {
+              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const RhoAct act = act2.half(c2);
+              const float x = hx[u];
+              const bool active = fabsf(x) > act.rho;
+              const float sgn = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
+              const float g_rho = active ? -sgn * gn[u] : 0.f;
+              float gx1, gx3;
+              rho_backward(params, x, sv[u], zz[u], act, g_rho, (i == j) ? 1.f : 2.f, g, gx1, gx3);
+#if UGLAD_CELL_BWD_GS
+              gS[base + i * D + j] += rho_backward_col(params, act, g_rho, 1);  // (upper triangle; mirrored with the G_B term at the end of the step)
+#endif
+              const float gh = (active ? gn[u] : 0.f) + gx1;
+              sY[i * LD + j] = gh;
+              sY[j * LD + i] = gh;
+              if (kPre) gz[u] = gx3;
+              else Go[i * D + j] = gx3;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+
+    KSTAMP(2);
+    using T = Tiles<NT, false>;
+    {
+      f32x16 acc[T::kPerWave];
+      // T1 = G_half U
+      gemm_lds<NT, false, false, false>(sY, sX, acc);
+      __syncthreads();
+      store_tiles<NT>(sY, acc);
+    }
+    __syncthreads();
+    KSTAMP(3);
+    float glam = 0.f;
+    {
+      // C = U^T T1 (symmetric: upper tiles) ; Y = C o F mirrored ; diagonal term of dL/dlam
+      f32x16 acc[TU::kPerWave];
+      gemm_lds<NT, true, false, true>(sX, sY, acc);
+      __syncthreads();
+      KSTAMP(4);
+#pragma unroll
+      for (int n = 0; n < TU::kPerWave; ++n) {
+        const int t = w + kWaves * n;
+        if (t < TU::kCount) {
+          int I, J;
+          TU::ij(t, I, J);
+          const int j = J * 32 + (lane & 31);
+          float aj[kNsIters], qj[kNsIters];
+#pragma unroll
+          for (int it = 0; it < kNsIters; ++it) {
+            aj[it] = s_a[it][j];
+            qj[it] = s_q[it][j];
+          }
+          const float rj = s_r[j], bj = s_beta[j];
+#pragma unroll
+          for (int e4 = 0; e4 < 4; ++e4) {  // accumulator entries 4 e4 .. 4 e4 + 3 sit in four consecutive rows
+            const int i0 = I * 32 + 8 * e4 + 4 * (lane >> 5);
+            float Kr[4];
+            if (mode == UGLAD_SQRT_EXACT) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) Kr[r] = 1.0f / (s_r[i0 + r] + rj);
+            } else {
+              float P[4] = {1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+              for (int it = 0; it < kNsIters; ++it) {  // one 16-byte LDS read per iterate covers the four rows
+                const f4 a4 = *reinterpret_cast<const f4*>(&s_a[it][i0]);
+                const f4 q4 = *reinterpret_cast<const f4*>(&s_q[it][i0]);
+                P[0] *= 0.5f * (3.f - q4.x - qj[it] + a4.x * aj[it]);
+                P[1] *= 0.5f * (3.f - q4.y - qj[it] + a4.y * aj[it]);
+                P[2] *= 0.5f * (3.f - q4.z - qj[it] + a4.z * aj[it]);
+                P[3] *= 0.5f * (3.f - q4.w - qj[it] + a4.w * aj[it]);
+              }
+              const float sc = 1.0f / (2.f * nrmR);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) Kr[r] = P[r] * sc;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int e = 4 * e4 + r, i = i0 + r;
+              if (I < J || i <= j) {
+                float v = 0.f;
+                if (i < D && j < D) {
+                  const float K = Kr[r];
+                  const float cij = acc[n][e];
+                  if (i == j) glam = fmaf(cij, -2.f * K * inv_lam2, glam);
+                  v = cij * 0.5f * fmaf(s_beta[i] + bj, K, -1.f);
+                }
+                sY[i * LD + j] = v;
+                sY[j * LD + i] = v;
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    KSTAMP(5);
+    {
+      // T2 = U (C o F)
+      f32x16 acc[T::kPerWave];
+      gemm_lds<NT, false, false, false>(sX, sY, acc);
+      __syncthreads();
+      store_tiles<NT>(sY, acc);
+    }
+    __syncthreads();
+    KSTAMP(6);
+    {
+      // G_B = T2 U^T (symmetric: upper tiles) -> LDS ; G_out = GZ_direct - G_B ; dL/dlam -= <S, G_B>/lam^2
+      f32x16 acc[TU::kPerWave];
+      gemm_lds<NT, false, true, true>(sY, sX, acc);
+      KSTAMP(7);
+      __syncthreads();  // every wave is done reading sY / sX
+#pragma unroll
+      for (int n = 0; n < TU::kPerWave; ++n) {
+        const int t = w + kWaves * n;
+        if (t < TU::kCount) {
+          int I, J;
+          TU::ij(t, I, J);
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sY[(I * 32 + acc_row(e, lane)) * LD + J * 32 + (lane & 31)] = acc[n][e];
+        }
+      }
+    }
+    __syncthreads();
+    KSTAMP(20);
+    {
+      int p = p0, c = c0;
+      for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
+        // all reads of a pass first, then the writes: G_out goes into G_B's own buffer, and read / write / read / ... of one LDS array
+        // is a chain of waits the compiler cannot reorder (19 k instead of 12 k ticks for this phase)
+        int pk[kQ];
+        float gb[kQ], sij[kQ];
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) {
+          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
+          advance(p, c);
+          const bool in = pk[u] >= 0;
+          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+          gb[u] = sY[in ? i * LD + j : 0];  // (unconditional reads, clamped addresses: no branch per entry)
+          // S_ij again from memory (L2: phase A read it this step) rather than 33 more registers held across the four products, which
+          // spilled dL/dZ's direct part (21 VGPRs, reloaded one round trip at a time right here: 8 k ticks)
+          sij[u] = Sm[in ? i * D + j : 0];
+        }
+        if (kPre) {
+          // branch-free: an entry that does not exist writes to the padding column (never read) and adds zero -- with a branch per entry the
+          // compiler loses count of the LDS operations in flight and waits for all of them before every pair of writes
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            const bool in = pk[u] >= 0;
+            const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+            const float o = gz[u] - gb[u];
+            sY[in ? i * LD + j : DP] = o;  // in G_B's place: (i, j) is read by this thread alone, (j, i) by nobody (G_B lives on the upper triangle)
+            sY[in ? j * LD + i : DP] = o;
+            glam = fmaf(in ? -sij[u] * inv_lam2 * ((i == j) ? 1.f : 2.f) : 0.f, gb[u], glam);
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            if (pk[u] >= 0) {
+              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const float o = Go[i * D + j] - gb[u];
+              sY[i * LD + j] = o;
+              sY[j * LD + i] = o;
+              glam = fmaf(-sij[u] * inv_lam2 * ((i == j) ? 1.f : 2.f), gb[u], glam);
+            }
+          }
+        }
+#if UGLAD_CELL_BWD_GS
+        {  // gS_ij += (G_B)_ij / lam_k, mirrored: only this thread touches gS_ij and gS_ji
+          const float inv_lam = 1.0f / lam;
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            if (pk[u] >= 0) {
+              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const float v = fmaf(gb[u], inv_lam, gS[base + i * D + j]);
+              gS[base + i * D + j] = v;
+              gS[base + j * D + i] = v;
+            }
+          }
+        }
+#endif
+      }
+    }
+    __syncthreads();
+    KSTAMP(21);
+    if (last) {  // coalesced copy-out
+      const int si = kThreads / D, sj = kThreads - si * D;
+      int i = tid / D, j = tid - i * D;
+      for (int idx = tid; idx < D * D; idx += kThreads) {
+        Go[idx] = sY[i * LD + j];
+        j += sj;
+        i += si;
+        if (j >= D) {
+          j -= D;
+          ++i;
+        }
+      }
+    }
+    KSTAMP(8);
+    // ---- reductions: dL/dlam of this step; the 28 rhoNN gradients once, after the last step
+    if (last) {
+#pragma unroll
+      for (int q = 0; q < kNRho; ++q) {
+        const float v = wave_sum(g[q]);
+        if (lane == 0) s_g[w][q] = v;
+      }
+    }
+    {
+      const float v = wave_sum(glam);
+      if (lane == 0) s_g[w][kNRho] = v;
+    }
+    __syncthreads();
+    if (tid == kNRho || (last && tid < kNRho)) {
+      float v = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < kWaves; ++ww) v += s_g[ww][tid];
+      if (tid < kNRho)
+        grad_rho_partial[(size_t)blockIdx.x * kNRho + tid] += v;
+      else
+        (glam_partial - (size_t)s * gridDim.x)[blockIdx.x] = v;
+    }
+    KSTAMP(9);
+  }
+}

@@ -243,6 +243,21 @@ __device__ __forceinline__ void rho_backward(const float* __restrict__ p, float 
   gx3 = ga1[0] * p[P_RW1 + 2] + ga1[1] * p[P_RW1 + 5] + ga1[2] * p[P_RW1 + 8];
 }
 
+// g_rho * d rho / d x_{col+1} (col 1: the S feature, col 2: Z_in) for the dL/dS kernels (cell_bwd.h, cell_gs_step_kernel).  The same
+// arithmetic as the d/dx1 and d/dx3 of rho_backward, which is left as it is (the kernels that call it keep their code).
+__device__ __forceinline__ float rho_backward_col(const float* __restrict__ p, const RhoAct& a, float g_rho, int col) {
+  const float go = g_rho * a.rho * (1.f - a.rho);
+  float ga2[3], ga1[3];
+#pragma unroll
+  for (int h = 0; h < 3; ++h) ga2[h] = go * p[P_RW3 + h] * (1.f - a.h2[h] * a.h2[h]);
+#pragma unroll
+  for (int h = 0; h < 3; ++h) {
+    const float s = ga2[0] * p[P_RW2 + h] + ga2[1] * p[P_RW2 + 3 + h] + ga2[2] * p[P_RW2 + 6 + h];
+    ga1[h] = s * (1.f - a.h1[h] * a.h1[h]);
+  }
+  return ga1[0] * p[P_RW1 + col] + ga1[1] * p[P_RW1 + 3 + col] + ga1[2] * p[P_RW1 + 6 + col];
+}
+
 // rho_backward for two entries at once (packed fp32 pipe); g2[q].x + g2[q].y is what the scalar version accumulates in g[q].
 __device__ __forceinline__ void rho_backward2(const float* __restrict__ p, v2f x1, v2f x2, v2f x3, const RhoAct2& a, v2f g_rho,
                                               v2f w, v2f* g2, v2f& gx1, v2f& gx3) {

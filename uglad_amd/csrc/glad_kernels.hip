@@ -344,390 +344,16 @@ __global__ __launch_bounds__(kThreads, 2) void cell_fwd_back_kernel(const float*
 // as in the forward epilogue; the thread that differentiates the threshold at (i,j) keeps the direct term dL/dZ_ij in a
 // register and adds (G_B)_ij, which comes back through LDS from the last GEMM, at the very end.  Symmetric products
 // (C = U^T G U, G_B) are formed on the 10 upper tiles only; the result leaves through LDS with coalesced stores.
-template <int NT>
-__global__ __launch_bounds__(kThreads) void cell_bwd_kernel(
-    const float* __restrict__ Gnext, const float* __restrict__ S, const float* __restrict__ Zin,
-    const float* __restrict__ half, const float* __restrict__ U, const float* __restrict__ beta,
-    const float* __restrict__ lam_ptr, const float* __restrict__ params, float* __restrict__ Gout,
-    float* __restrict__ grad_rho_partial, float* __restrict__ glam_partial, float* __restrict__ gws, int D, int mode,
-    int gs, int k_count, int lam_stride) {
-  constexpr int DP = NT * 32, LD = DP + 1;
-  UGLAD_BIG_BUFFERS(sX, DP * LD, sY, DP * LD, gws)  // U ; G -> G_half -> T -> C o F -> T2
-  __shared__ float s_beta[DP], s_r[DP];
-  __shared__ __attribute__((aligned(16))) float s_a[kNsIters][DP];  // NS10: a_i^(t) ...
-  __shared__ __attribute__((aligned(16))) float s_q[kNsIters][DP];  // ... and its square
-  __shared__ float s_red[8];
-  __shared__ float s_g[kWaves][kNRho + 1];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const size_t base = (size_t)blockIdx.x * D * D;
-  const float* Sm = S + base;
-  const float* Gm = Gnext + base;
-  float* Go = Gout + base;
-  const int grp = blockIdx.x / gs;
-  params += (size_t)grp * kNParam;
-  // k_count consecutive steps k, k-1, ... of the unrolled pass in ONE launch (DP <= 128 only): the pointers name step k, step k - s sits
-  // s slabs (gridDim.x matrices) below.  dL/dZ stays in LDS from one step to the next -- the two big buffers swap roles -- the 28 rhoNN
-  // gradient sums stay in registers, and only the last step writes G_out.  k_count = 1 is the per-step entry point.
-  const size_t step_mdd = (size_t)gridDim.x * D * D, step_md = (size_t)gridDim.x * D;
-  float g[kNRho];
-#pragma unroll
-  for (int q = 0; q < kNRho; ++q) g[q] = 0.f;
-#pragma unroll 1
-  for (int s = 0; s < k_count; ++s) {
-    const bool first = (s == 0), last = (s == k_count - 1);
-    const int tid = opaque_v(threadIdx.x), lane = tid & 63;  // (shadow the outer ones: nothing per-thread is hoisted)
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the tile indices derived from it live in SGPRs)
-    const float* Zm = Zin + base - s * step_mdd;
-    const float* Hm = half + base - s * step_mdd;
-    const float* Um = U + base - s * step_mdd;
-    const float* bm = beta + (size_t)blockIdx.x * D - s * step_md;
-    const float lam = lam_ptr[(long)grp - (long)s * lam_stride];
-    const float c4 = 4.0f / lam, inv_lam2 = 1.0f / (lam * lam);
-
-    KSTAMP(0);
-    // U -> sX, and in the first step G_next -> sY (afterwards G is there already): row-major, coalesced, 8 loads in flight per thread.
-    // The loads are unconditional (a clamped address, the value selected afterwards): with `in ? load : 0` the compiler put every load
-    // behind its own branch and an s_waitcnt vmcnt(0), one round trip after the other (30 k instead of 17 k ticks for this phase).
-    // (Explicit loops, not a helper taking the destination as a pointer: through a pointer parameter the LDS stores become flat stores
-    // that may alias the loads, and the loop serialises completely -- 137 k ticks.)
-    if (first) {  // 16 loads in flight per thread
-      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
-        float u[8], gv[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          const int i = idx / DP, k = idx - i * DP;
-          const bool in = (idx < DP * DP) && i < D && k < D;
-          const int at = in ? i * D + k : 0;
-          const float xu = Um[at], xg = Gm[at];
-          u[q] = in ? xu : 0.f;
-          gv[q] = in ? xg : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          if (idx < DP * DP) {
-            const int i = idx / DP, k = idx - i * DP;
-            sX[i * LD + k] = u[q];
-            sY[i * LD + k] = gv[q];
-          }
-        }
-      }
-    } else {
-      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
-        float u[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          const int i = idx / DP, k = idx - i * DP;
-          const bool in = (idx < DP * DP) && i < D && k < D;
-          const float xu = Um[in ? i * D + k : 0];
-          u[q] = in ? xu : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          if (idx < DP * DP) {
-            const int i = idx / DP, k = idx - i * DP;
-            sX[i * LD + k] = u[q];
-          }
-        }
-      }
-    }
-    float a2 = 0.f;
-    if (tid < D) {
-      const float be = bm[tid];
-      const float al = fmaf(be, be, c4);
-      a2 = al * al;
-    }
-    const float nrmA = sqrtf(block_sum(a2, s_red));
-    float r2 = 0.f;
-    if (tid < DP) {
-      float be = 0.f, r = 1.f;
-      if (tid < D) {
-        be = bm[tid];
-        r = sqrt_spectrum(be, c4, nrmA, mode);
-        r2 = r * r;
-      }
-      s_beta[tid] = be;
-      s_r[tid] = r;
-    }
-    const float nrmR = sqrtf(block_sum(r2, s_red));
-    if (mode == UGLAD_SQRT_NS10 && tid < DP) {
-      float a = s_r[tid] / nrmR;
-#pragma unroll
-      for (int it = 0; it < kNsIters; ++it) {
-        s_a[it][tid] = a;
-        s_q[it][tid] = a * a;
-        a = 0.5f * a * (3.f - a * a);
-      }
-    }
-    __syncthreads();
-
-    KSTAMP(1);
-    // ---- phase A: rhoNN + threshold backward on the upper triangle (entry e = tid + kThreads q, as in the forward cell)
-    using TU = Tiles<NT, true>;
-    constexpr int kMaxQ = ((DP / 2) * (DP + 1) + kThreads - 1) / kThreads;
-    constexpr bool kPre = DP <= 128;          // all entries of a thread in registers at once
-    constexpr int kQ = kPre ? kMaxQ : 8;      // entries per thread and pass
-    const int D1 = D + 1, total = ((D + 1) / 2) * D1;
-    const int sp = kThreads / D1, sc = kThreads - sp * D1;
-    const int p0 = tid / D1, c0 = tid - p0 * D1;
-    auto entry = [&](int e, int p, int c) -> int {  // (i << 16) | j of entry (pair p, offset c), -1 when there is none
-      if (e >= total) return -1;
-      if (c < D - p) return (p << 16) | (p + c);
-      const int i = D - 1 - p;
-      return (i == p) ? -1 : ((i << 16) | (i + (c - (D - p))));
-    };
-    auto advance = [&](int& p, int& c) {
-      c += sc;
-      p += sp;
-      if (c >= D1) {
-        c -= D1;
-        ++p;
-      }
-    };
-    float gz[kQ];  // dL/dZ_in, direct part (through rhoNN's third input); DP > 128: parked in G_out's upper triangle instead
-    {
-      int p = p0, c = c0;
-      for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
-        int pk[kQ];
-        float hx[kQ], zz[kQ], gn[kQ], sv[kQ];
-#pragma unroll
-        for (int u = 0; u < kQ; ++u) {
-          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
-          advance(p, c);
-          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-          const bool in = pk[u] >= 0;
-          if (kPre) gz[u] = 0.f;
-          hx[u] = in ? Hm[i * D + j] : 0.f;
-          zz[u] = in ? Zm[i * D + j] : 0.f;
-          sv[u] = in ? Sm[i * D + j] : 0.f;
-          gn[u] = in ? ((i == j) ? sY[i * LD + j] : 0.5f * (sY[i * LD + j] + sY[j * LD + i])) : 0.f;
-        }
-        // forward activations of two entries at a time on the packed fp32 pipe, the backward entry by entry (packed, its 28
-        // accumulators would need a second set of registers that the kernel does not have)
-        constexpr int kQ2 = (kQ + 1) / 2;
-#pragma unroll
-        for (int h = 0; h < kQ2; ++h) {
-          const int u0 = 2 * h, u1 = (2 * h + 1 < kQ) ? 2 * h + 1 : 2 * h;
-          const bool has1 = 2 * h + 1 < kQ;
-          if (!has1 && pk[u0] < 0) continue;  // (the odd one out exists on a few threads only)
-          RhoAct2 act2;
-          rho_forward2(params, (v2f){hx[u0], has1 ? hx[u1] : 0.f}, (v2f){sv[u0], has1 ? sv[u1] : 0.f},
-                       (v2f){zz[u0], has1 ? zz[u1] : 0.f}, act2);
-#pragma unroll
-          for (int c2 = 0; c2 < 2; ++c2) {
-            const int u = c2 ? u1 : u0;
-            if ((c2 == 0 || has1) && pk[u] >= 0) {
-              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-              const RhoAct act = act2.half(c2);
-              const float x = hx[u];
-              const bool active = fabsf(x) > act.rho;
-              const float sgn = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
-              const float g_rho = active ? -sgn * gn[u] : 0.f;
-              float gx1, gx3;
-              rho_backward(params, x, sv[u], zz[u], act, g_rho, (i == j) ? 1.f : 2.f, g, gx1, gx3);
-              const float gh = (active ? gn[u] : 0.f) + gx1;
-              sY[i * LD + j] = gh;
-              sY[j * LD + i] = gh;
-              if (kPre) gz[u] = gx3;
-              else Go[i * D + j] = gx3;
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-
-    KSTAMP(2);
-    using T = Tiles<NT, false>;
-    {
-      f32x16 acc[T::kPerWave];
-      // T1 = G_half U
-      gemm_lds<NT, false, false, false>(sY, sX, acc);
-      __syncthreads();
-      store_tiles<NT>(sY, acc);
-    }
-    __syncthreads();
-    KSTAMP(3);
-    float glam = 0.f;
-    {
-      // C = U^T T1 (symmetric: upper tiles) ; Y = C o F mirrored ; diagonal term of dL/dlam
-      f32x16 acc[TU::kPerWave];
-      gemm_lds<NT, true, false, true>(sX, sY, acc);
-      __syncthreads();
-      KSTAMP(4);
-#pragma unroll
-      for (int n = 0; n < TU::kPerWave; ++n) {
-        const int t = w + kWaves * n;
-        if (t < TU::kCount) {
-          int I, J;
-          TU::ij(t, I, J);
-          const int j = J * 32 + (lane & 31);
-          float aj[kNsIters], qj[kNsIters];
-#pragma unroll
-          for (int it = 0; it < kNsIters; ++it) {
-            aj[it] = s_a[it][j];
-            qj[it] = s_q[it][j];
-          }
-          const float rj = s_r[j], bj = s_beta[j];
-#pragma unroll
-          for (int e4 = 0; e4 < 4; ++e4) {  // accumulator entries 4 e4 .. 4 e4 + 3 sit in four consecutive rows
-            const int i0 = I * 32 + 8 * e4 + 4 * (lane >> 5);
-            float Kr[4];
-            if (mode == UGLAD_SQRT_EXACT) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) Kr[r] = 1.0f / (s_r[i0 + r] + rj);
-            } else {
-              float P[4] = {1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-              for (int it = 0; it < kNsIters; ++it) {  // one 16-byte LDS read per iterate covers the four rows
-                const f4 a4 = *reinterpret_cast<const f4*>(&s_a[it][i0]);
-                const f4 q4 = *reinterpret_cast<const f4*>(&s_q[it][i0]);
-                P[0] *= 0.5f * (3.f - q4.x - qj[it] + a4.x * aj[it]);
-                P[1] *= 0.5f * (3.f - q4.y - qj[it] + a4.y * aj[it]);
-                P[2] *= 0.5f * (3.f - q4.z - qj[it] + a4.z * aj[it]);
-                P[3] *= 0.5f * (3.f - q4.w - qj[it] + a4.w * aj[it]);
-              }
-              const float sc = 1.0f / (2.f * nrmR);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) Kr[r] = P[r] * sc;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int e = 4 * e4 + r, i = i0 + r;
-              if (I < J || i <= j) {
-                float v = 0.f;
-                if (i < D && j < D) {
-                  const float K = Kr[r];
-                  const float cij = acc[n][e];
-                  if (i == j) glam = fmaf(cij, -2.f * K * inv_lam2, glam);
-                  v = cij * 0.5f * fmaf(s_beta[i] + bj, K, -1.f);
-                }
-                sY[i * LD + j] = v;
-                sY[j * LD + i] = v;
-              }
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    KSTAMP(5);
-    {
-      // T2 = U (C o F)
-      f32x16 acc[T::kPerWave];
-      gemm_lds<NT, false, false, false>(sX, sY, acc);
-      __syncthreads();
-      store_tiles<NT>(sY, acc);
-    }
-    __syncthreads();
-    KSTAMP(6);
-    {
-      // G_B = T2 U^T (symmetric: upper tiles) -> LDS ; G_out = GZ_direct - G_B ; dL/dlam -= <S, G_B>/lam^2
-      f32x16 acc[TU::kPerWave];
-      gemm_lds<NT, false, true, true>(sY, sX, acc);
-      KSTAMP(7);
-      __syncthreads();  // every wave is done reading sY / sX
-#pragma unroll
-      for (int n = 0; n < TU::kPerWave; ++n) {
-        const int t = w + kWaves * n;
-        if (t < TU::kCount) {
-          int I, J;
-          TU::ij(t, I, J);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) sY[(I * 32 + acc_row(e, lane)) * LD + J * 32 + (lane & 31)] = acc[n][e];
-        }
-      }
-    }
-    __syncthreads();
-    KSTAMP(20);
-    {
-      int p = p0, c = c0;
-      for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
-        // all reads of a pass first, then the writes: G_out goes into G_B's own buffer, and read / write / read / ... of one LDS array
-        // is a chain of waits the compiler cannot reorder (19 k instead of 12 k ticks for this phase)
-        int pk[kQ];
-        float gb[kQ], sij[kQ];
-#pragma unroll
-        for (int u = 0; u < kQ; ++u) {
-          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
-          advance(p, c);
-          const bool in = pk[u] >= 0;
-          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-          gb[u] = sY[in ? i * LD + j : 0];  // (unconditional reads, clamped addresses: no branch per entry)
-          // S_ij again from memory (L2: phase A read it this step) rather than 33 more registers held across the four products, which
-          // spilled dL/dZ's direct part (21 VGPRs, reloaded one round trip at a time right here: 8 k ticks)
-          sij[u] = Sm[in ? i * D + j : 0];
-        }
-        if (kPre) {
-          // branch-free: an entry that does not exist writes to the padding column (never read) and adds zero -- with a branch per entry the
-          // compiler loses count of the LDS operations in flight and waits for all of them before every pair of writes
-#pragma unroll
-          for (int u = 0; u < kQ; ++u) {
-            const bool in = pk[u] >= 0;
-            const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-            const float o = gz[u] - gb[u];
-            sY[in ? i * LD + j : DP] = o;  // in G_B's place: (i, j) is read by this thread alone, (j, i) by nobody (G_B lives on the upper triangle)
-            sY[in ? j * LD + i : DP] = o;
-            glam = fmaf(in ? -sij[u] * inv_lam2 * ((i == j) ? 1.f : 2.f) : 0.f, gb[u], glam);
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < kQ; ++u) {
-            if (pk[u] >= 0) {
-              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-              const float o = Go[i * D + j] - gb[u];
-              sY[i * LD + j] = o;
-              sY[j * LD + i] = o;
-              glam = fmaf(-sij[u] * inv_lam2 * ((i == j) ? 1.f : 2.f), gb[u], glam);
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    KSTAMP(21);
-    if (last) {  // coalesced copy-out
-      const int si = kThreads / D, sj = kThreads - si * D;
-      int i = tid / D, j = tid - i * D;
-      for (int idx = tid; idx < D * D; idx += kThreads) {
-        Go[idx] = sY[i * LD + j];
-        j += sj;
-        i += si;
-        if (j >= D) {
-          j -= D;
-          ++i;
-        }
-      }
-    }
-    KSTAMP(8);
-    // ---- reductions: dL/dlam of this step; the 28 rhoNN gradients once, after the last step
-    if (last) {
-#pragma unroll
-      for (int q = 0; q < kNRho; ++q) {
-        const float v = wave_sum(g[q]);
-        if (lane == 0) s_g[w][q] = v;
-      }
-    }
-    {
-      const float v = wave_sum(glam);
-      if (lane == 0) s_g[w][kNRho] = v;
-    }
-    __syncthreads();
-    if (tid == kNRho || (last && tid < kNRho)) {
-      float v = 0.f;
-#pragma unroll
-      for (int ww = 0; ww < kWaves; ++ww) v += s_g[ww][tid];
-      if (tid < kNRho)
-        grad_rho_partial[(size_t)blockIdx.x * kNRho + tid] += v;
-      else
-        (glam_partial - (size_t)s * gridDim.x)[blockIdx.x] = v;
-    }
-    KSTAMP(9);
-  }
-}
+#define UGLAD_CELL_BWD_NAME cell_bwd_kernel
+#define UGLAD_CELL_BWD_GS 0
+#include "cell_bwd.h"
+#undef UGLAD_CELL_BWD_NAME
+#undef UGLAD_CELL_BWD_GS
+#define UGLAD_CELL_BWD_NAME cell_bwd_gs_kernel
+#define UGLAD_CELL_BWD_GS 1
+#include "cell_bwd.h"
+#undef UGLAD_CELL_BWD_NAME
+#undef UGLAD_CELL_BWD_GS
 
 #ifndef UGLAD_TU_NT
 }  // namespace uglad
@@ -1004,6 +630,65 @@ __global__ __launch_bounds__(kThreads) void init_bwd_kernel(const float* __restr
   if (tid == 0) gt_partial[blockIdx.x] = -sum;
 }
 
+// Theta_0 = (S + t I)^-1 with respect to S:  gS -= Theta0 sym(G0) Theta0.  T = Theta0 G0 on all tiles, then T Theta0 on the upper tiles,
+// subtracted from gS_ij and mirrored into gS_ji (exactly symmetric).  The 42 parameter gradients stay with init_bwd_kernel.
+template <int NT>
+__global__ __launch_bounds__(kThreads) void init_bwd_gs_kernel(const float* __restrict__ theta0, const float* __restrict__ G0,
+                                                               float* __restrict__ gS, float* __restrict__ gws, int D) {
+  constexpr int DP = NT * 32, LD = DP + 1;
+  UGLAD_BIG_BUFFERS(sX, DP * LD, sY, DP * LD, gws)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const size_t base = (size_t)blockIdx.x * D * D;
+  for (int idx = tid; idx < DP * DP; idx += kThreads) {
+    const int i = idx / DP, k = idx - i * DP;
+    const bool in = i < D && k < D;
+    sX[i * LD + k] = in ? theta0[base + i * D + k] : 0.f;
+    sY[i * LD + k] = in ? 0.5f * (G0[base + i * D + k] + G0[base + k * D + i]) : 0.f;
+  }
+  __syncthreads();
+  {
+    f32x16 acc[Tiles<NT, false>::kPerWave];
+    gemm_lds<NT, false, false, false>(sX, sY, acc);
+    __syncthreads();
+    store_tiles<NT>(sY, acc);
+  }
+  __syncthreads();
+  using T = Tiles<NT, true>;
+  f32x16 acc[T::kPerWave];
+  gemm_lds<NT, false, false, true>(sY, sX, acc);
+#pragma unroll
+  for (int n = 0; n < T::kPerWave; ++n) {
+    const int t = w + kWaves * n;
+    if (t < T::kCount) {
+      int I, J;
+      T::ij(t, I, J);
+      const int j = J * 32 + (lane & 31);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = I * 32 + acc_row(e, lane);
+        if (i <= j && j < D) {
+          const float v = gS[base + i * D + j] - acc[n][e];
+          gS[base + i * D + j] = v;
+          if (i != j) gS[base + j * D + i] = v;
+        }
+      }
+    }
+  }
+}
+
+#ifndef UGLAD_TU_NT
+// Theta_0 = diag(1 / (S_ii + t)) with respect to S:  gS_ii -= G0_ii Theta0_ii^2.  One thread per diagonal entry.
+__global__ void init_bwd_diag_gs_kernel(const float* __restrict__ theta0, const float* __restrict__ G0, float* __restrict__ gS, int D,
+                                        size_t total) {
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t m = idx / D;
+    const size_t at = m * D * D + (idx - m * D) * (D + 1);
+    const float d = theta0[at];
+    gS[at] -= G0[at] * d * d;
+  }
+}
+#endif
+
 #ifndef UGLAD_TU_NT
 __global__ __launch_bounds__(kThreads) void init_bwd_diag_kernel(const float* __restrict__ theta0,
                                                                  const float* __restrict__ G0,
@@ -1169,6 +854,113 @@ __global__ void loss_bwd_kernel(const float* __restrict__ theta, const float* __
       v += tanhf(theta[idx] * mask) * mask;
     }
     Gout[idx] = gs * v;
+  }
+}
+
+// dL/dS of the loss, symmetric part: gS_b = g_up[0] * scale * sum over the matrices m that read S_b of (Theta_m + Theta_m^T) / 2
+// (one S broadcast against all M matrices when s_batch = 1).  Overwrites gS (s_batch, D, D); a fixed order of the sum over m.
+__global__ void loss_bwd_gs_kernel(const float* __restrict__ theta, const float* __restrict__ g_up, float scale, float* __restrict__ gS,
+                                   int s_batch, int M, int D) {
+  const float gs = g_up[0] * scale * 0.5f;
+  const size_t dd = (size_t)D * D, total = (size_t)s_batch * dd;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t sb = idx / dd;
+    const int r = (int)(idx - sb * dd);
+    const int i = r / D, j = r - i * D;
+    float v = 0.f;
+    for (size_t m = sb; m < (size_t)M; m += s_batch) v += theta[m * dd + i * D + j] + theta[m * dd + j * D + i];
+    gS[idx] = gs * v;
+  }
+}
+
+// dL/dS of one step on the paths whose kernels have no dL/dS variant (the many-workgroups backward, csrc/wide_bwd.h, and the matrix
+// iteration, csrc/wide_ns.h), behind their unchanged launches: per upper-triangle entry (i, j) the rhoNN / threshold backward of the step
+// is evaluated again from G_next, theta_half, S and Z_in -- the S-feature term, and the Z_in-feature term gz that the step's G_out holds
+// together with -G_B (G_out = gz - G_B) -- and gS_ij += (gz - sym(G_out))_ij / lam_k + the S-feature term, mirrored into gS_ji.
+__global__ __launch_bounds__(256) void cell_gs_step_kernel(const float* __restrict__ Gnext, const float* __restrict__ S,
+                                                           const float* __restrict__ Zin, const float* __restrict__ half,
+                                                           const float* __restrict__ lam_ptr, const float* __restrict__ params,
+                                                           const float* __restrict__ Gout, float* __restrict__ gS, int D, int gs,
+                                                           size_t total) {
+  const size_t dd = (size_t)D * D;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t m = idx / dd;
+    const int r = (int)(idx - m * dd);
+    const int i = r / D, j = r - i * D;
+    if (j < i) continue;
+    const size_t ij = m * dd + r, ji = m * dd + (size_t)j * D + i;
+    const int grp = (int)(m / gs);
+    const float* p = params + (size_t)grp * kNParam;
+    const float lam = lam_ptr[grp];
+    const float gn = (i == j) ? Gnext[ij] : 0.5f * (Gnext[ij] + Gnext[ji]);
+    const float x = half[ij];
+    RhoAct act;
+    rho_forward(p, x, S[ij], Zin[ij], act);
+    const bool active = fabsf(x) > act.rho;
+    const float sgn = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
+    const float g_rho = active ? -sgn * gn : 0.f;
+    const float gz = rho_backward_col(p, act, g_rho, 2);
+    const float go = (i == j) ? Gout[ij] : 0.5f * (Gout[ij] + Gout[ji]);
+    const float v = gS[ij] + (gz - go) / lam + rho_backward_col(p, act, g_rho, 1);
+    gS[ij] = v;
+    gS[ji] = v;
+  }
+}
+
+// C_m = A_m B_m for M matrices of D x D (fp32; 64 x 64 output tile per workgroup, 4 x 4 per thread, k in chunks of 16 through LDS): the
+// Theta_0 term of dL/dS beyond the one-workgroup kernels' size.
+__global__ __launch_bounds__(256) void gs_gemm_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C, int D) {
+  __shared__ float sA[16][65], sB[16][65];
+  const size_t base = (size_t)blockIdx.z * D * D;
+  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+  for (int k0 = 0; k0 < D; k0 += 16) {
+    for (int e = threadIdx.x; e < 1024; e += 256) {
+      const int ar = e >> 4, ac = e & 15, gi = i0 + ar, gk = k0 + ac;
+      sA[ac][ar] = (gi < D && gk < D) ? A[base + (size_t)gi * D + gk] : 0.f;
+      const int br = e >> 6, bc = e & 63, bk = k0 + br, bj = j0 + bc;
+      sB[br][bc] = (bk < D && bj < D) ? B[base + (size_t)bk * D + bj] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      float a[4], b[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[q] = sA[k][4 * ty + q];
+        b[q] = sB[k][4 * tx + q];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[u][v] = fmaf(a[u], b[v], acc[u][v]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = i0 + 4 * ty + u;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int j = j0 + 4 * tx + v;
+      if (i < D && j < D) C[base + (size_t)i * D + j] = acc[u][v];
+    }
+  }
+}
+
+// gS -= (R + R^T) / 2, elementwise over M matrices (exactly symmetric when gS is)
+__global__ void gs_sub_sym_kernel(const float* __restrict__ R, float* __restrict__ gS, int D, size_t total) {
+  const size_t dd = (size_t)D * D;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t m = idx / dd;
+    const int r = (int)(idx - m * dd);
+    const int i = r / D, j = r - i * D;
+    gS[idx] -= 0.5f * (R[idx] + R[m * dd + (size_t)j * D + i]);
   }
 }
 #endif
@@ -1751,6 +1543,12 @@ __global__ __launch_bounds__(kThreads) void symeig_jacobi_kernel(const float* __
   X void symeig_lean_kernel<NT>(float*, float*, const float*, float*, int);                                                    \
   X void cell_fwd_lean_kernel<NT>(const float*, const float*, const float*, const float*, float*, float*, float*, float*,     \
                                   float*, float*, const float*, float*, int, int, int, int, LamStep);
+// the dL/dS variants (uglad_glad_backward_wrt_s) in translation units of their own (-DUGLAD_TU_GS): instantiated next to the kernels above
+// they changed how the compiler treated cell_bwd_kernel<3> (80 instead of 78 SGPR spills, scripts/kernel_meta.py)
+#define UGLAD_PER_NT_GS(X, NT)                                                                                                  \
+  X void cell_bwd_gs_kernel<NT>(const float*, const float*, const float*, const float*, const float*, const float*, const float*, \
+                                const float*, float*, float*, float*, float*, int, int, int, int, int, float*);                  \
+  X void init_bwd_gs_kernel<NT>(const float*, const float*, float*, float*, int);
 #define UGLAD_PER_NT_SMALL(X, NT)                                                                                       \
   X void symeig_jacobi_kernel<NT>(const float*, float*, float*, int);                                                  \
   X void chol_init_kernel<NT>(const float*, const float*, float*, int*, int, int);                                     \
@@ -1782,6 +1580,8 @@ template __global__ void cell_bwd_kernel<UGLAD_TU_NT>(const float*, const float*
 UGLAD_PER_NT_TRIWAVE(template __global__, UGLAD_TU_NT)
 #elif defined(UGLAD_TU_NT) && defined(UGLAD_DEV_ONLY_CHOL)
 UGLAD_PER_NT_SMALL(template __global__, UGLAD_TU_NT)
+#elif defined(UGLAD_TU_NT) && defined(UGLAD_TU_GS)
+UGLAD_PER_NT_GS(template __global__, UGLAD_TU_NT)
 #elif defined(UGLAD_TU_NT)
 UGLAD_PER_NT_KERNELS(template __global__, UGLAD_TU_NT)
 UGLAD_PER_NT_DIAG(template __global__, UGLAD_TU_NT)
@@ -1797,7 +1597,8 @@ UGLAD_PER_NT_TRIWAVE(template __global__, UGLAD_TU_NT)
 UGLAD_PER_NT_BIG(template __global__, UGLAD_TU_NT)
 #endif
 #elif defined(UGLAD_TU_HOST)
-#define UGLAD_DECLARE_NT(NT) UGLAD_PER_NT_KERNELS(extern template __global__, NT) UGLAD_PER_NT_DIAG(extern template __global__, NT)
+#define UGLAD_DECLARE_NT(NT) UGLAD_PER_NT_KERNELS(extern template __global__, NT) UGLAD_PER_NT_DIAG(extern template __global__, NT) \
+  UGLAD_PER_NT_GS(extern template __global__, NT)
 UGLAD_DECLARE_NT(1) UGLAD_DECLARE_NT(2) UGLAD_DECLARE_NT(3) UGLAD_DECLARE_NT(4)
 UGLAD_PER_NT_SMALL(extern template __global__, 1) UGLAD_PER_NT_SMALL(extern template __global__, 2)
 UGLAD_PER_NT_SMALL(extern template __global__, 3) UGLAD_PER_NT_SMALL(extern template __global__, 4)
@@ -2579,11 +2380,28 @@ int uglad_cell_bwd(const float* G_next, const float* S, const float* Z_in, const
 // All arrays are the whole-pass ones (step-major, as uglad_glad_backward takes them); G_out receives dL/dZ_0.
 static int launch_cell_bwd_all_steps(const float* G_L, const float* S, const float* Z, const float* half, const float* U,
                                      const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
-                                     float* glam_partial, int L, int M, int D, int sqrt_mode, hipStream_t st) {
+                                     float* glam_partial, int L, int M, int D, int sqrt_mode, hipStream_t st, float* gS = nullptr) {
   const size_t mdd = (size_t)M * D * D, last = (size_t)(L - 1);
+  if (gS) {
+    DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((cell_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_L, S, Z + last * mdd,
+                                            half + last * mdd, U + last * mdd, beta + last * M * D, lam + last * t_groups, params, G_out,
+                                            grad_rho_partial, glam_partial + last * M, nullptr, D, sqrt_mode, group_size(M), L, t_groups,
+                                            gS));
+    return launch_status();
+  }
   DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((cell_bwd_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_L, S, Z + last * mdd, half + last * mdd,
                                           U + last * mdd, beta + last * M * D, lam + last * t_groups, params, G_out, grad_rho_partial,
                                           glam_partial + last * M, nullptr, D, sqrt_mode, group_size(M), L, t_groups));
+  return launch_status();
+}
+
+// One step of the backward pass that also accumulates dL/dS into gS: the spectral path's one-workgroup cell (uglad_cell_bwd's last case;
+// uglad_glad_backward_wrt_s has refused the passes that take its other two paths).
+static int launch_cell_bwd_step_gs(const float* G_next, const float* S, const float* Z_in, const float* half, const float* U,
+                                   const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
+                                   float* glam_partial, float* workspace, int M, int D, int sqrt_mode, float* gS, hipStream_t st) {
+  DISPATCH_NT(D, hipLaunchKernelGGL((cell_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_next, S, Z_in, half, U, beta, lam, params,
+                                    G_out, grad_rho_partial, glam_partial, workspace, D, sqrt_mode, group_size(M), 1, 0, gS));
   return launch_status();
 }
 
@@ -2633,6 +2451,17 @@ int uglad_loss_bwd(const float* theta, const float* theta_inv, const float* S, i
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, theta, theta_inv, S, s_batch,
                      struct_theta, g_up, scale, G_out, D, total);
+  return launch_status();
+}
+
+int uglad_loss_bwd_wrt_s(const float* theta, const float* theta_inv, const float* S, int s_batch, const float* struct_theta,
+                         const float* g_up, float scale, float* G_out, float* gS, int M, int D, uglad_stream_t stream) {
+  if (!gS) return UGLAD_E_NULL;
+  int rc = uglad_loss_bwd(theta, theta_inv, S, s_batch, struct_theta, g_up, scale, G_out, M, D, stream);
+  if (rc) return rc;
+  const size_t total = (size_t)s_batch * D * D;
+  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  hipLaunchKernelGGL(loss_bwd_gs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, theta, g_up, scale, gS, s_batch, M, D);
   return launch_status();
 }
 
@@ -2712,7 +2541,8 @@ static int enqueue_glad_forward(const float* S, const float* params, float lambd
 static int enqueue_glad_backward(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
                                  const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
                                  float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
-                                 float* grad, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream) {
+                                 float* grad, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream,
+                                 float* gS = nullptr) {
   if (!G_L || !S || !params || !Z || !half || !U || !beta || !lam || !lam_in || !gbuf0 || !gbuf1 || !grad_rho_partial ||
       !glam_partial || !gt_partial || !grad)
     return UGLAD_E_NULL;
@@ -2721,22 +2551,56 @@ static int enqueue_glad_backward(const float* G_L, const float* S, const float* 
   const size_t mdd = (size_t)M * D * D;
   int rc = zero_floats(grad_rho_partial, (size_t)M * UGLAD_NRHO, (hipStream_t)stream);
   if (rc) return rc;
+  if (gS && (rc = zero_floats(gS, mdd, (hipStream_t)stream))) return rc;
   const float* cur = G_L;
   if (D <= 128 && !ns_wanted(D) && !wide_wanted(M, D) && persistent_bwd_enabled()) {
     if ((rc = launch_cell_bwd_all_steps(G_L, S, Z, half, U, beta, lam, params, gbuf0, grad_rho_partial, glam_partial, L, M, D, sqrt_mode,
-                                        (hipStream_t)stream)))
+                                        (hipStream_t)stream, gS)))
       return rc;
     cur = gbuf0;
   } else
   for (int k = L - 1; k >= 0; --k) {
     float* out = (k & 1) ? gbuf1 : gbuf0;
-    rc = uglad_cell_bwd(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
-                        lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M, D,
-                        sqrt_mode, stream);
+    if (gS && (ns_path(M, D, true, sqrt_mode) || wide_wanted(M, D))) {  // no dL/dS variant there: the step as it is, then its dL/dS
+      rc = uglad_cell_bwd(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
+                          lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M, D,
+                          sqrt_mode, stream);
+      if (rc) return rc;
+      const int grid = (int)((mdd + 255) / 256 < 4096 ? (mdd + 255) / 256 : 4096);
+      hipLaunchKernelGGL(cell_gs_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, cur, S, Z + (size_t)k * mdd,
+                         half + (size_t)k * mdd, lam + (size_t)k * t_groups, params, (const float*)out, gS, D, group_size(M), mdd);
+      rc = launch_status();
+    } else if (gS)
+      rc = launch_cell_bwd_step_gs(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
+                                   lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M,
+                                   D, sqrt_mode, gS, (hipStream_t)stream);
+    else
+      rc = uglad_cell_bwd(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
+                          lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M, D,
+                          sqrt_mode, stream);
     if (rc) return rc;
     cur = out;
   }
   if ((rc = uglad_init_theta_bwd(Z, cur, init_diag, gt_partial, workspace, M, D, stream))) return rc;
+  if (gS) {  // the Theta_0 term of dL/dS
+    hipStream_t st = (hipStream_t)stream;
+    if (init_diag == 1) {
+      const size_t total = (size_t)M * D;
+      const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+      hipLaunchKernelGGL(init_bwd_diag_gs_kernel, dim3(grid), dim3(256), 0, st, (const float*)Z, cur, gS, D, total);
+    } else if (ns_factorisation(M, D)) {  // beyond the one-workgroup kernels: T = Theta0 G0 into the idle G buffer, R = T Theta0 into G0's
+      float* T = (cur == gbuf0) ? gbuf1 : gbuf0;
+      float* R = const_cast<float*>(cur);
+      const dim3 tiles((D + 63) / 64, (D + 63) / 64, M);
+      hipLaunchKernelGGL(gs_gemm_kernel, tiles, dim3(256), 0, st, (const float*)Z, cur, T, D);
+      hipLaunchKernelGGL(gs_gemm_kernel, tiles, dim3(256), 0, st, (const float*)T, (const float*)Z, R, D);
+      const int grid = (int)((mdd + 255) / 256 < 4096 ? (mdd + 255) / 256 : 4096);
+      hipLaunchKernelGGL(gs_sub_sym_kernel, dim3(grid), dim3(256), 0, st, (const float*)R, gS, D, mdd);
+    } else {
+      DISPATCH_NT(D, hipLaunchKernelGGL((init_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, Z, cur, gS, workspace, D));
+    }
+    if ((rc = launch_status())) return rc;
+  }
   return uglad_finish_grads(gt_partial, grad_rho_partial, glam_partial, lam_in, params, grad, L, M, stream);
 }
 
@@ -2777,6 +2641,20 @@ int uglad_glad_backward_grouped(const float* G_L, const float* S, const float* p
   GroupScope scope(groups);
   return uglad_glad_backward(G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial,
                              glam_partial, gt_partial, grad, workspace, M, D, sqrt_mode, stream);
+}
+
+int uglad_glad_backward_wrt_s(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
+                              const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
+                              float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
+                              float* grad, float* workspace, int M, int D, int groups, int sqrt_mode, float* gS, uglad_stream_t stream) {
+  if (!gS || (D > 128 && !workspace)) return UGLAD_E_NULL;
+  if (groups < 1 || M < groups || M % groups != 0) return UGLAD_E_DIM;
+  CHECK_DIMS(M, D);
+  if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
+  if (init_diag != 0 && init_diag != 1) return UGLAD_E_MODE;
+  GroupScope scope(groups);
+  return enqueue_glad_backward(G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial, glam_partial,
+                               gt_partial, grad, workspace, M, D, sqrt_mode, stream, gS);
 }
 
 // ---- the sharded pass as ONE call (collective site i)

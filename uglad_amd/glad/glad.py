@@ -134,7 +134,7 @@ class _GladUnrolled(torch.autograd.Function):
         lib = _lib.get_lib()
         M, D, _ = S.shape
         dev = S.device
-        train = ctx.needs_input_grad[1]
+        train = ctx.needs_input_grad[1] or ctx.needs_input_grad[0]  # (the backward pass with respect to S needs the same state)
         f32 = dict(dtype=torch.float32, device=dev)
         params = params.detach().contiguous()
         lam = torch.empty(L + 1, **f32)
@@ -197,10 +197,20 @@ class _GladUnrolled(torch.autograd.Function):
         gt_partial = torch.empty(M, **f32)
         grad = torch.empty(_lib.NPARAM, **f32)
         wsp = lib.workspace(M, D, S)  # read by the beyond-LDS instantiations (D > 128) only
+        # dL/dS (symmetric part, include/uglad_hip.h) when S needs it: S is local to the rank, so a sharded pass exchanges nothing for it
+        gS = torch.empty(M, D, D, **f32) if ctx.needs_input_grad[0] else None
         # the parameter gradients are sums over the LOCAL matrices; a sharded caller all-reduces them (uglad_amd/dist.py)
         lib.glad_backward(G.contiguous(), S, params, init_diag, L, Z, half, U, beta, lam, lam_in, bufs[0], bufs[1],
-                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode)
-        return None, grad, None, None, None, None, None, None
+                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, gS=gS)
+        return gS, grad if ctx.needs_input_grad[1] else None, None, None, None, None, None, None
+
+
+def _input_covariance(Sb: Tensor, device) -> Tensor:
+    """Sb as the kernels take it (contiguous fp32 on `device`); kept in the autograd graph when it requires grad and grad mode is on,
+    detached otherwise."""
+    if not (Sb.requires_grad and torch.is_grad_enabled()):
+        Sb = Sb.detach()
+    return Sb.to(device=device, dtype=torch.float32).contiguous()
 
 
 def glad(
@@ -220,6 +230,10 @@ def glad(
 
     When the batch is sharded over ranks, `collective` carries the per-step SUM of the batch-wide norm and
     `global_batch` is the number of matrices over all ranks (the divisor of get_frobenius_norm's batch mean).
+
+    Sb stays in the autograd graph when it requires grad (and grad mode is on), as in the reference: Sb.grad is then the SYMMETRIC
+    part (G + G^T) / 2 of the reference's gradient G, in Sb's dtype and on its device (include/uglad_hip.h,
+    uglad_glad_backward_wrt_s), on every backward path.  Otherwise Sb is detached as before.
     """
     if sqrt_mode is None:
         sqrt_mode = DEFAULT_SQRT_MODE
@@ -230,7 +244,7 @@ def glad(
     if Sb.dim() == 2:
         Sb = Sb.reshape(1, Sb.shape[0], Sb.shape[1])
     params = model.packed()
-    Sb = Sb.detach().to(device=params.device, dtype=torch.float32).contiguous()
+    Sb = _input_covariance(Sb, params.device)
     coll = collective if collective is not None else get_collective()
     if global_batch is None and coll.world_size > 1:
         # (the shards of a batch that does not divide evenly differ in size: the divisor of the batch mean cannot be guessed locally)
@@ -251,7 +265,7 @@ class _GladGrouped(torch.autograd.Function):
         lib = _lib.get_lib()
         M, D, _ = S.shape
         G = params.shape[0]
-        train = ctx.needs_input_grad[1]
+        train = ctx.needs_input_grad[1] or ctx.needs_input_grad[0]
         f32 = dict(dtype=torch.float32, device=S.device)
         params = params.detach().contiguous()
         lam = torch.empty(L + 1, G, **f32)
@@ -294,9 +308,10 @@ class _GladGrouped(torch.autograd.Function):
         gt_partial = torch.empty(M, **f32)
         grad = torch.empty(G, _lib.NPARAM, **f32)
         wsp = lib.workspace(M, D, S)
+        gS = torch.empty(M, D, D, **f32) if ctx.needs_input_grad[0] else None
         lib.glad_backward(Gout.contiguous(), S, params, init_diag, L, Z, half, U, beta, lam, lam_in, bufs[0], bufs[1],
-                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, groups=G)
-        return None, grad, None, None, None, None
+                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, groups=G, gS=gS)
+        return gS, grad if ctx.needs_input_grad[1] else None, None, None, None, None
 
 
 def glad_grouped(Sb: Tensor, params: Tensor, lambda_init: float = 1, L: int = 15, INIT_DIAG: int = 0,
@@ -312,5 +327,5 @@ def glad_grouped(Sb: Tensor, params: Tensor, lambda_init: float = 1, L: int = 15
         raise ValueError("INIT_DIAG must be 0 or 1")
     if params.dim() != 2 or params.shape[1] != _lib.NPARAM or Sb.dim() != 3 or Sb.shape[0] % params.shape[0] != 0:
         raise ValueError("params must be (G, 42) and Sb (M, D, D) with M a multiple of G")
-    Sb = Sb.detach().to(device=params.device, dtype=torch.float32).contiguous()
+    Sb = _input_covariance(Sb, params.device)  # (in the graph when it requires grad: as in glad())
     return _GladGrouped.apply(Sb, params, int(L), int(INIT_DIAG), float(lambda_init), _lib.SQRT_MODES[sqrt_mode])

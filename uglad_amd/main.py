@@ -54,6 +54,10 @@ class _GlassoLoss(torch.autograd.Function):
         theta, theta_inv, S, struct = ctx.saved_tensors
         G = torch.empty_like(theta)
         g_up = g.detach().to(torch.float32).reshape(1).contiguous()
+        if ctx.needs_input_grad[1]:  # dL/dS, symmetric part (include/uglad_hip.h, uglad_loss_bwd_wrt_s)
+            gS = torch.empty_like(S)
+            lib.loss_bwd_wrt_s(theta, theta_inv, S, struct if ctx.has_struct else None, g_up, ctx.scale, G, gS)
+            return G, gS, None, None
         lib.loss_bwd(theta, theta_inv, S, struct if ctx.has_struct else None, g_up, ctx.scale, G)
         return G, None, None, None
 
@@ -62,9 +66,13 @@ def loss_uGLAD(theta: torch.Tensor, S: torch.Tensor, struct_theta: Optional[torc
                batch_divisor: Optional[int] = None) -> torch.Tensor:
     """Glasso objective sum_b(-logdet Theta_b + tr(S_b Theta_b)) / B with B = S.shape[0] (ref main.py:289-335), plus the
     log-cosh structure penalty when `struct_theta` is given.  S may be (1, D, D) against Theta (K, D, D) (the
-    missing-data call, main.py:620-622; the divisor is then 1).  `batch_divisor` overrides B for a sharded batch."""
+    missing-data call, main.py:620-622; the divisor is then 1).  `batch_divisor` overrides B for a sharded batch.
+    S stays in the autograd graph when it requires grad (and grad mode is on): S.grad is the symmetric part of the reference's
+    gradient, (Theta + Theta^T) / 2 per matrix, summed over the batch when one S is broadcast.  Otherwise S is detached as before."""
     dev = theta.device
-    S = S.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if not (S.requires_grad and torch.is_grad_enabled()):
+        S = S.detach()
+    S = S.to(device=dev, dtype=torch.float32).contiguous()
     if S.dim() == 2:
         S = S[None]
     if S.shape[0] not in (1, theta.shape[0]):
