@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of two builds of the library on bench.py's workload: alternates UGLAD_LIB=<A> and the in-tree build, N rounds, prints ms/step and
 # the per-kernel HIP-event launch times of every run.   bash scripts/ab_bench.sh scripts/_build/libuglad_r3.so [rounds=3] [bench args...]
-set -u
+set -u -o pipefail
 cd "$(dirname "$0")/.."
 A=$1; N=${2:-3}; shift; shift
 mkdir -p gpurun_out

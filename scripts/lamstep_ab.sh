@@ -1,6 +1,6 @@
 #!/bin/bash
-# Same-box A/B (GPU box) of the lambda step carried by the forward cell's second launch (LamStep, glad_kernels.hip: thread 0 when a group holds one
-# matrix, the last workgroup of the group to arrive otherwise) against its own norm_lambda launch (UGLAD_NO_FUSED_LAMBDA=1).
+# Same-box A/B (GPU box) of the lambda step carried by the forward cell's second launch (LamStep, glad_kernels.hip: thread 0 of the workgroup when a
+# group holds one matrix; groups of several matrices keep the separate launch -- Route::fuse_lambda, host_route.h) against its own norm_lambda launch (UGLAD_NO_FUSED_LAMBDA=1).
 #   bash scripts/lamstep_ab.sh c1     BASELINE config 1, medians of individually synchronised passes, three alternating rounds
 #   bash scripts/lamstep_ab.sh bench  bench.py at config 3 (the headline) and config 2, three alternating rounds; final_loss must agree to the bit
 cd "$(dirname "$0")/.."

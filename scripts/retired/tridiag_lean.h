@@ -3,7 +3,7 @@
 // series -- was wrong: with the round trips cut from twelve to four per step the chain still takes 2170 cycles and the sweep 1776
 // (old: 2020 / 1540).  A wave issues one instruction every ~5 cycles whatever it is; the step is bound by the NUMBER of instructions
 // on its critical wave (chain ~250 + sweep ~170), and this form has more of them (four rows per chain lane: every elementwise
-// operation four times; copies at the switch entry).  Not compiled by anything; it was wired into LAUNCH_TRIDIAG (glad_kernels.hip)
+// operation four times; copies at the switch entry).  Not compiled by anything; it was wired into the tridiagonalisation launch (now launch_tridiag, host_launch.h)
 // as tridiag_lean_kernel<NT> for NT <= 4 behind UGLAD_TRIDIAG_LEAN.
 //
 // Householder tridiagonalisation for D <= 128, latency-lean (round 3).  Same algorithm, same outputs and the same resources per workgroup

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B (GPU box) of the one-wave tridiagonalisation (tridiag_wave.h, D <= 64) against the workgroup kernel (UGLAD_TRIDIAG_WAVE=0) on
+# Same-box A/B (GPU box) of the one-wave tridiagonalisation (tridiag_wave.h, D <= 32) against the workgroup kernel (UGLAD_TRIDIAG_WAVE=0) on
 # bench.py's pass at several (M, D, L): ms per pass, forward-only rate and the HIP-event launch times, two alternating rounds.
 set -u
 cd "$(dirname "$0")/.."

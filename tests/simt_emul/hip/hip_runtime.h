@@ -15,11 +15,14 @@
 #include <stdlib.h>
 #include <string.h>
 #include <ucontext.h>
+#include <cxxabi.h>
+#include <dlfcn.h>
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #define __global__
@@ -435,8 +438,39 @@ inline float atomicAdd(float* p, float v) { const float o = *p; *p = o + v; retu
 inline hipError_t hipMemcpyFromSymbol(void* dst, const void* sym, size_t n) { memcpy(dst, sym, n); return hipSuccess; }
 
 
+// Launch trace (tests/test_launch_routes.py): UGLAD_EMUL_LAUNCH_LOG=<file> appends one line per launch -- the kernel's demangled symbol,
+// grid, block and every scalar / pointer argument (structs by size only) -- and UGLAD_EMUL_RECORD_ONLY=1 records without executing, so
+// the host layer's decisions can be pinned with pointers that are never dereferenced.
+namespace simt {
+template <class T>
+inline void trace_arg(FILE* f, const T& a) {
+  if constexpr (std::is_pointer_v<T> || std::is_null_pointer_v<T>) fprintf(f, " %p", (const void*)a);
+  else if constexpr (std::is_floating_point_v<T>) fprintf(f, " %.9g", (double)a);
+  else if constexpr (std::is_arithmetic_v<T> || std::is_enum_v<T>) fprintf(f, " %lld", (long long)a);
+  else fprintf(f, " {%zu}", sizeof(T));
+}
+template <class K, class... Args>
+inline bool trace_launch(K kernel, dim3 g, dim3 b, const Args&... args) {
+  const char* path = getenv("UGLAD_EMUL_LAUNCH_LOG");
+  if (!path) return true;
+  if (FILE* f = fopen(path, "a")) {
+    Dl_info info{};
+    int st = -1;
+    char* name = dladdr(reinterpret_cast<void*>(kernel), &info) && info.dli_sname ? abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st) : nullptr;
+    fprintf(f, "%s [%u %u %u] [%u %u %u]", st == 0 ? name : (info.dli_sname ? info.dli_sname : "?"), g.x, g.y, g.z, b.x, b.y, b.z);
+    free(name);
+    (trace_arg(f, args), ...);
+    fputc('\n', f);
+    fclose(f);
+  }
+  const char* only = getenv("UGLAD_EMUL_RECORD_ONLY");
+  return !(only && only[0] == '1');
+}
+}  // namespace simt
+
 template <class K, class... Args>
 inline void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, size_t, hipStream_t, Args... args) {
+  if (!simt::trace_launch(kernel, grid, block, args...)) return;
   for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
       for (unsigned b = 0; b < grid.x; ++b) simt::run_block(grid, block, dim3(b, by, bz), [&]() { kernel(args...); });

@@ -26,8 +26,12 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(dll, name), name
     assert dll.uglad_max_dim() >= 128 and dll.uglad_version() >= 1  # pure host calls, no GPU needed
-    src = open(os.path.join(ROOT, "uglad_amd", "csrc", "glad_kernels.hip")).read()
-    assert "__HIP_PLATFORM" not in src and "cuda" not in src.lower()  # gfx950 only, no dual path
+    csrc = os.path.join(ROOT, "uglad_amd", "csrc")
+    sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    assert "glad_kernels.hip" in sources and "host_route.h" in sources
+    for f in sources:  # gfx950 only, no dual path -- in the kernels and in the host layer's headers
+        src = open(os.path.join(csrc, f)).read()
+        assert "__HIP_PLATFORM" not in src and "cuda" not in src.lower(), f
 
 
 def test_product_has_no_cpu_fallback_and_never_touches_the_oracle(monkeypatch):

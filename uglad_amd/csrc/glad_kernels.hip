@@ -1612,1302 +1612,10 @@ UGLAD_PER_NT_BIG(extern template __global__, 7) UGLAD_PER_NT_BIG(extern template
 }  // namespace uglad
 
 #ifndef UGLAD_TU_NT
-// =============================================================================================== C ABI
-using namespace uglad;
-
-// UGLAD_MAX_NT (default 8): the largest instantiated NT = ceil(D / 32).  Test builds (sanitizer, emulator) lower it to keep their
-// compile time down; UGLAD_NO_BIG is the older spelling of UGLAD_MAX_NT=4.
-#ifndef UGLAD_MAX_NT
-#ifdef UGLAD_NO_BIG
-#define UGLAD_MAX_NT 4
-#else
-#define UGLAD_MAX_NT 8
-#endif
-#endif
-#define UGLAD_MAX_EIG_DIM (32 * UGLAD_MAX_NT)  // the spectral path: eigensolver, LDS / slab-resident kernels templated on NT
-#define UGLAD_MAX_DIM (kNsMaxD > UGLAD_MAX_EIG_DIM ? kNsMaxD : UGLAD_MAX_EIG_DIM)  // beyond it the matrix-iteration path (wide_ns.h)
-// cond(b^T b + 4/lam I) up to which reference-made goldens sit inside the 1e-4 tolerance on Theta (tests/golden/regime_sweep.json:
-// every case up to cond 708 within 1.1e-5 of the fp64 value of its own function; the min-max-normalised fit that runs to convergence,
-// tests/golden/fit_direct_converged.npz, reaches 1.03e3 with precision_ 2.0e-5 from the reference; the case at 4.4e3 is 1.04e-4 off:
-// DESIGN.md section 2).  Round 3 had 1000 here, BELOW a case its own goldens validate -- that fit warned.
-#define UGLAD_VALIDATED_COND 1500.0f
-
-static inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
-// UGLAD_NT_MASK (test builds only: bit k set = NT = k is instantiated; default all): the sanitizer build compiles just the padded
-// sizes its script uses, which halves its compile time.  A size that is masked out is refused like one beyond UGLAD_MAX_DIM.
-#ifndef UGLAD_NT_MASK
-#define UGLAD_NT_MASK 0x1fe
-#endif
-#define UGLAD_HAS_NT(k) (((UGLAD_NT_MASK) >> (k)) & 1)
-#define CHECK_DIMS_EIG(M, D) /* entry points that exist on the spectral path only */ \
-  do {                                                    \
-    if ((M) < 1 || (D) < 1 || (D) > UGLAD_MAX_EIG_DIM || !UGLAD_HAS_NT(((D) + 31) / 32)) return UGLAD_E_DIM; \
-  } while (0)
-#define CHECK_DIMS(M, D) /* the path itself: any D up to UGLAD_MAX_DIM */ \
-  do {                                                    \
-    if ((M) < 1 || (D) < 1 || (D) > UGLAD_MAX_DIM || ((D) <= UGLAD_MAX_EIG_DIM && !UGLAD_HAS_NT(((D) + 31) / 32))) return UGLAD_E_DIM; \
-    if (((D) > UGLAD_MAX_EIG_DIM || ns_wanted(D)) && (M) > kNsMaxBatch) return UGLAD_E_DIM; \
-  } while (0)
-// (the matrix iteration's launches carry matrix x product, up to three products, in one grid dimension of at most 65535)
-constexpr int kNsMaxBatch = 65535 / 3;
-static bool ns_wanted(int D);
-
-// dispatch on NT = ceil(D / 32): every padded size has its own instantiation; beyond NT = 4 (D > 128) the kernels keep their
-// two D x D buffers in the caller's workspace instead of LDS
-#if UGLAD_HAS_NT(1)
-#define DISPATCH_NT1(...) case 1: { constexpr int NT = 1; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT1(...)
-#endif
-#if UGLAD_HAS_NT(2)
-#define DISPATCH_NT2(...) case 2: { constexpr int NT = 2; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT2(...)
-#endif
-#if UGLAD_HAS_NT(3)
-#define DISPATCH_NT3(...) case 3: { constexpr int NT = 3; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT3(...)
-#endif
-#if UGLAD_HAS_NT(4)
-#define DISPATCH_NT4(...) case 4: { constexpr int NT = 4; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT4(...)
-#endif
-#if UGLAD_MAX_NT >= 5 && UGLAD_HAS_NT(5)
-#define DISPATCH_NT5(...) case 5: { constexpr int NT = 5; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT5(...)
-#endif
-#if UGLAD_MAX_NT >= 6 && UGLAD_HAS_NT(6)
-#define DISPATCH_NT6(...) case 6: { constexpr int NT = 6; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT6(...)
-#endif
-#if UGLAD_MAX_NT >= 7 && UGLAD_HAS_NT(7)
-#define DISPATCH_NT7(...) case 7: { constexpr int NT = 7; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT7(...)
-#endif
-#if UGLAD_MAX_NT >= 8 && UGLAD_HAS_NT(8)
-#define DISPATCH_NT8(...) case 8: { constexpr int NT = 8; __VA_ARGS__; } break;
-#else
-#define DISPATCH_NT8(...)
-#endif
-#define DISPATCH_NT(D, ...)          \
-  switch (((D) + 31) / 32) {          \
-    DISPATCH_NT1(__VA_ARGS__) DISPATCH_NT2(__VA_ARGS__) DISPATCH_NT3(__VA_ARGS__) DISPATCH_NT4(__VA_ARGS__) \
-    DISPATCH_NT5(__VA_ARGS__) DISPATCH_NT6(__VA_ARGS__) DISPATCH_NT7(__VA_ARGS__) DISPATCH_NT8(__VA_ARGS__) \
-    default: break; /* unreachable: CHECK_DIMS */ \
-  }
-#define DISPATCH_NT_SMALL(D, ...) /* kernels instantiated for NT <= 4 only */ \
-  switch (((D) + 31) / 32) {          \
-    DISPATCH_NT1(__VA_ARGS__) DISPATCH_NT2(__VA_ARGS__) DISPATCH_NT3(__VA_ARGS__) DISPATCH_NT4(__VA_ARGS__) \
-    default: break; \
-  }
-static inline int padded_dim(int D) { return ((D + 31) / 32) * 32; }
-static inline long long big_floats_rt(int DP) { return 2LL * (((long long)DP * (DP + 1) + 3) & ~3LL); }  // = big_floats<DP>()
-
-static std::atomic<int> g_wide_mode{-2};  // -2: not set (UGLAD_WIDE_BWD in the environment decides, else automatic); -1 auto, 0 never, 1 always
-
-extern "C" {
-
-int uglad_version(void) { return 3; }
-float uglad_validated_cond(void) { return UGLAD_VALIDATED_COND; }
-int uglad_set_wide_mode(int mode) {
-  if (mode < -1 || mode > 1) return UGLAD_E_MODE;
-  g_wide_mode.store(mode, std::memory_order_relaxed);
-  return 0;
-}
-int uglad_max_dim(void) { return UGLAD_MAX_DIM; }
-int uglad_max_eig_dim(void) { return UGLAD_MAX_EIG_DIM; }
-
-// The matrix-iteration path (wide_ns.h).  Modes: -1 automatic (below), 0 only beyond the eigensolver's size, 1 for every D (tests, A/B
-// measurements).  UGLAD_MATRIX_ITERATION=0/1 in the environment presets it when nothing was set.
-// Automatic: beyond the eigensolver's size always; and for FEW matrices of 128 < D <= 256, where one workgroup's Householder chain is
-// most of the spectral cell while the iteration's products use the whole chip -- measured over a grid of (D, batch), ms per 15-step pass
-// spectral vs iteration (profiles/r03_ns_crossover.txt): training D = 256: 1 matrix 16.9 vs 9.4, 6: 17.3 vs 15.4, 8: 17.5 vs 18.6; D = 192:
-// 8: 12.5 vs 12.2, 16: 12.7 vs 18.1; D = 160: 8: 11.3 vs 10.0; forward only D = 256: 1: 15.5 vs 4.2, 16: 16.1 vs 9.7, 64: 17.2 vs 27.7.
-// Only for UGLAD_SQRT_NS10.
-static std::atomic<int> g_ns_mode{-2};
-int uglad_set_matrix_iteration(int mode) {
-  if (mode < -1 || mode > 1) return UGLAD_E_MODE;
-  g_ns_mode.store(mode, std::memory_order_relaxed);
-  return 0;
-}
-static int ns_mode() {
-  int mode = g_ns_mode.load(std::memory_order_relaxed);
-  if (mode == -2) {
-    const char* e = std::getenv("UGLAD_MATRIX_ITERATION");
-    const int env_mode = (e && e[0] == '1') ? 1 : ((e && e[0] == '0') ? 0 : -1);
-    int expected = -2;
-    mode = g_ns_mode.compare_exchange_strong(expected, env_mode, std::memory_order_relaxed) ? env_mode : expected;
-  }
-  return mode;
-}
-// forced for this size whatever the batch: by the mode, or because no eigensolver exists
-static bool ns_wanted(int D) { return ns_mode() == 1 || D > UGLAD_MAX_EIG_DIM; }
-// Theta_0, its gradient and the loss's logdet / inverse on the factorisation of wide_ns.h (L D L^T + Newton steps) instead of the
-// eigensolver: wherever there is none, and for the few large matrices the cell itself takes to the matrix-iteration path (one
-// 256 x 256 matrix: 0.35 ms against 0.9 ms for the eigen path's tridiagonalisation, merges, back-transformation and products)
-static bool ns_path(int M, int D, bool training, int sqrt_mode);
-static bool ns_factorisation(int M, int D) {
-  return D > UGLAD_MAX_EIG_DIM || (D > 128 && (ns_path(M, D, true, UGLAD_SQRT_NS10) || ns_path(M, D, false, UGLAD_SQRT_NS10)));
-}
-// the products' all-chunks-in-flight form (wide_ns.h, PRE): D <= 4 k chunks of the 32 x 32 tiling; UGLAD_NS_PREFETCH_ALL=0 in the environment: off (A/B)
-static bool ns_prefetch_all(int D) {
-  const char* e = std::getenv("UGLAD_NS_PREFETCH_ALL");
-  return D <= 4 * NsTile<32>::kK && !(e && e[0] == '0');
-}
-// the path of a cell call: training = the call saves state for a backward pass (which must take the same path)
-static bool ns_path(int M, int D, bool training, int sqrt_mode) {
-  if (ns_wanted(D)) return true;
-  if (ns_mode() != -1 || sqrt_mode != UGLAD_SQRT_NS10 || D <= 128) return false;
-  const long long tiles = (long long)M * wide_tiles(D) * wide_tiles(D);
-  return training ? (tiles <= 96 && M <= 8) : tiles <= 256;
-}
-extern "C" int uglad_cond_is_upper_bound(int M, int D, int training, int sqrt_mode) {
-  if (M < 1 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  return ns_path(M, D, training != 0, sqrt_mode) ? 1 : 0;
-}
-// per matrix: the header every path uses and, behind all headers, this matrix's region: kNsSlabs D x D fp64 slabs and one fp32 slab
-// (G_half) -- or, for the factorisations beyond the eigensolver's size, the three padded fp32 slabs of the L D L^T inverse and one more
-// D x D for the Newton steps' residual, whichever is larger
-struct NsLayout {
-  size_t hdr, region;  // floats
-  size_t dslab, dregion;  // doubles: one slab, one matrix's region
-  float* H;
-  float* W;    // region of matrix m: W + m * region
-  double* Wd;  // the same as fp64: slab s of matrix m at Wd + m * dregion + s * dslab
-  float* Gh;   // the fp32 slab of matrix m: Gh + m * region
-};
-static NsLayout ns_layout(float* workspace, int M, int D) {
-  const int DP = padded_dim(D);
-  NsLayout l;
-  l.hdr = 3 * (size_t)DP + (size_t)(DP / 32) * 1024;
-  // (the header also holds this path's per-tile sums and scalars, wide_ns.h: past D = 1900 they outgrow the size the other paths' layout gives it)
-  const size_t need = (size_t)ns_off_dbl(D) + 2 * ((size_t)ns_tiles_max(D) + 4 + (size_t)wide_tiles(D)) + 8;
-  if (need > l.hdr) l.hdr = (need + 3) & ~(size_t)3;
-  l.dslab = (size_t)D * D;
-  l.region = 2 * kNsSlabs * l.dslab + l.dslab;
-  const size_t fact = 3 * (size_t)ns_fact_dim(D) * (ns_fact_dim(D) + 1) + l.dslab;
-  if (D > 128 && fact > l.region) l.region = fact;  // (D <= 128: Theta_0 and the loss use the LDS Cholesky kernels on every path)
-  l.region = (l.region + 3) & ~(size_t)3;  // (16-byte granularity: vector loads of the slabs)
-  l.dregion = l.region / 2;
-  l.H = workspace;
-  l.W = workspace ? workspace + (size_t)M * l.hdr : nullptr;
-  l.Wd = reinterpret_cast<double*>(l.W);
-  l.Gh = l.W ? l.W + 2 * kNsSlabs * l.dslab : nullptr;
-  return l;
-}
-int uglad_workspace_floats(int M, int D) {
-  if (M < 1 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const int DP = padded_dim(D);
-  long long n = 0;
-  if (D <= UGLAD_MAX_EIG_DIM) n = (long long)M * (3 * DP + (DP / 32) * 1024) + (DP > 128 ? (long long)M * big_floats_rt(DP) : 0);
-  if (ns_path(M, D, true, UGLAD_SQRT_NS10) || ns_path(M, D, false, UGLAD_SQRT_NS10)) {  // (either kind of call may take the matrix-iteration path at this shape)
-    const NsLayout l = ns_layout(nullptr, M, D);
-    const long long nn = (long long)M * (long long)(l.hdr + l.region);
-    if (nn > n) n = nn;
-  }
-  return n > 2147483647LL ? UGLAD_E_DIM : (int)n;
-}
-
-// Groups: the batch may consist of G independent problems of M / G consecutive matrices each, every one with its own 42
-// parameters and its own lambda sequence (the folds of CV mode in one launch: uglad_glad_forward_grouped).  The per-step
-// entry points keep their single-group meaning; the grouped whole-pass calls set the group count for their duration.
-static thread_local int t_groups = 1;
-struct GroupScope {
-  int saved;
-  explicit GroupScope(int g) : saved(t_groups) { t_groups = g; }
-  ~GroupScope() { t_groups = saved; }
-};
-static inline int group_size(int M) { return M / t_groups > 0 ? M / t_groups : 1; }
-
-// the tridiagonalisation launch every eigendecomposition starts with (tridiag.h); R = the D x D slab of each matrix that
-// will receive that matrix's final output
-#define LAUNCH_TRIDIAG(A0, A1, LAMP, RBASE, TRI) LAUNCH_TRIDIAG_IF(A0, A1, LAMP, RBASE, TRI, (const int*)nullptr)
-/* ONLY: per-matrix flags (0 = skip this matrix) or nullptr = all */
-// UGLAD_TRIDIAG_SMALL=0 in the environment: 512 threads also for D <= 96 (A/B measurements)
-static bool tridiag_small_enabled() {  // (8 column groups, 64 NT threads, measured as well: slower at every size, profiles/r04_tridiag_small.txt)
-  static const bool on = [] {
-    const char* e = std::getenv("UGLAD_TRIDIAG_SMALL");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// UGLAD_TRIDIAG_WAVE=0: the workgroup kernel also for D <= 64 (A/B measurements; read on every call: tests flip it)
-static bool tridiag_wave_enabled() {
-  const char* e = std::getenv("UGLAD_TRIDIAG_WAVE");
-  return !(e && e[0] == '0');
-}
-#define LAUNCH_TRIDIAG_IF(A0, A1, LAMP, RBASE, TRI, ONLY)                                                                     \
-  DISPATCH_NT(D, if constexpr (NT == 1) {                                                                                     \
-    if (tridiag_wave_enabled()) { /* one wave per matrix, no barriers (tridiag_wave.h; NT = 2 measured slower) */             \
-      hipLaunchKernelGGL((tridiag_wave_kernel<NT>), dim3(M), dim3(64), 0, st, A0, A1, LAMP, RBASE, TRI, D, group_size(M), ONLY); \
-      break;                                                                                                                  \
-    }                                                                                                                         \
-  } if constexpr (NT <= 3) {                                                                                                  \
-    if (tridiag_small_enabled()) {                                                                                            \
-      hipLaunchKernelGGL((tridiag_kernel<NT, 128 * NT>), dim3(M), dim3(128 * NT), 0, st, A0, A1, LAMP, RBASE, TRI, D,         \
-                         group_size(M), ONLY);                                                                                \
-      break;                                                                                                                  \
-    }                                                                                                                         \
-  } if constexpr (NT > 4) {                                                                                                   \
-    if (M <= 256) { /* few large matrices: one workgroup per CU anyway, 1024 threads hide the sweep's latency (tridiag.h) */  \
-      hipLaunchKernelGGL((tridiag_kernel<NT, 1024>), dim3(M), dim3(1024), 0, st, A0, A1, LAMP, RBASE, TRI, D, group_size(M),  \
-                         ONLY);                                                                                               \
-      break;                                                                                                                  \
-    }                                                                                                                         \
-  } hipLaunchKernelGGL((tridiag_kernel<NT, kThreads>), dim3(M), dim3(kThreads), 0, st, A0, A1, LAMP, RBASE, TRI, D,           \
-                       group_size(M), ONLY))
-
-// D <= 128: Theta_0 and the loss's logdet / inverse by blocked Cholesky (chol.h); the eigen path follows only for matrices the
-// Cholesky kernel flagged (not positive definite, NaN).  UGLAD_CHOLESKY=0 in the environment: the eigen path for all (A/B measurements).
-static bool cholesky_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("UGLAD_CHOLESKY");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// UGLAD_PERSISTENT_BWD=0: one launch per step of the backward pass also for D <= 128 (read on every call: tests flip it)
-static bool persistent_bwd_enabled() {
-  const char* e = std::getenv("UGLAD_PERSISTENT_BWD");
-  return !(e && e[0] == '0');
-}
-// the per-matrix flags live at the head of the workspace region the forward cell uses for its triangular factors (idle here)
-static int* chol_flags(float* workspace, int M, int D) { return reinterpret_cast<int*>(workspace + (size_t)M * 3 * padded_dim(D)); }
-
-static bool wide_wanted(int M, int D);
-static void launch_ns_inverse(const float* A, const float* shift, int shift_stride, float* out, float* logdet_out, float* workspace, int M, int D,
-                              hipStream_t st);
-static void launch_wide_inverse(const float* A, const float* shift, int shift_stride, float* out, float* workspace, int M, int D,
-                                hipStream_t st);
-
-int uglad_init_theta(const float* S, const float* params, int init_diag, float* theta0, float* workspace, int M, int D,
-                     uglad_stream_t stream) {
-  if (!S || !params || !theta0 || (init_diag == 0 && !workspace)) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  hipStream_t st = (hipStream_t)stream;
-  if (init_diag == 1) {
-    const size_t total = (size_t)M * D * D;
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(init_diag_kernel, dim3(grid), dim3(256), 0, st, S, params, theta0, D, total, group_size(M));
-  } else if (init_diag == 0 && ns_factorisation(M, D)) {
-    launch_ns_inverse(S, params + P_T, kNParam, theta0, nullptr, workspace, M, D, st);
-  } else if (init_diag == 0) {
-    const int* only = nullptr;
-    if (D <= 128 && cholesky_enabled()) {
-      int* flags = chol_flags(workspace, M, D);
-      DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((chol_init_kernel<NT>), dim3(M), dim3(kThreads), 0, st, S, params, theta0, flags, D,
-                                              group_size(M)));
-      only = flags;
-    }
-    LAUNCH_TRIDIAG_IF(S, (const float*)nullptr, (const float*)nullptr, theta0, workspace, only);
-    if (wide_wanted(M, D)) {
-      launch_wide_inverse(S, params + P_T, kNParam, theta0, workspace, M, D, st);
-    } else {
-      DISPATCH_NT(D, hipLaunchKernelGGL((init_inverse_kernel<NT>), dim3(M), dim3(kThreads), 0, st, S, params, theta0,
-                                        workspace, D, group_size(M), only));
-    }
-  } else {
-    return UGLAD_E_MODE;
-  }
-  return launch_status();
-}
-
-int uglad_init_theta_bwd(const float* theta0, const float* G0, int init_diag, float* gt_partial, float* workspace, int M,
-                         int D, uglad_stream_t stream) {
-  if (!theta0 || !G0 || !gt_partial || (D > 128 && init_diag == 0 && !workspace)) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  hipStream_t st = (hipStream_t)stream;
-  if (init_diag == 1) {
-    hipLaunchKernelGGL(init_bwd_diag_kernel, dim3(M), dim3(kThreads), 0, st, theta0, G0, gt_partial, D);
-  } else if (init_diag == 0 && ns_factorisation(M, D)) {  // gt_partial = -<G0^T, Theta0 Theta0>, one workgroup per tile of the product
-    const NsLayout l = ns_layout(workspace, M, D);
-    const int nt = wide_tiles(D);
-    WideFwd fw{};
-    fw.X = G0;
-    fw.x_stride = (size_t)D * D;
-    hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiDotT>), dim3(nt, nt, M), dim3(kWThreads), 0, st, theta0, (size_t)D * D, theta0,
-                       (size_t)D * D, (float*)nullptr, (size_t)0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, l.H,
-                       l.hdr, ns_off_tiles(D), D, 0, group_size(M), D, D, D, fw);
-    hipLaunchKernelGGL(ns_tile_sum_kernel, dim3((M + 63) / 64), dim3(64), 0, st, (const float*)l.H, l.hdr, gt_partial, -1.f, M, D);
-  } else if (init_diag == 0) {
-    DISPATCH_NT(D, hipLaunchKernelGGL((init_bwd_kernel<NT>), dim3(M), dim3(kThreads), 0, st, theta0, G0, gt_partial, workspace,
-                                      D));
-  } else {
-    return UGLAD_E_MODE;
-  }
-  return launch_status();
-}
-
-int uglad_lambda_init(const float* params, float lambda_init, float* lam_out, float* lam_in, uglad_stream_t stream) {
-  if (!params || !lam_out || !lam_in) return UGLAD_E_NULL;
-  hipLaunchKernelGGL(lambda_init_kernel, dim3((t_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream, params, lambda_init,
-                     lam_out, lam_in, t_groups);
-  return launch_status();
-}
-
-// Few, large matrices: many workgroups per matrix (wide_bwd.h) -- the backward cell as six short launches, the forward cell's
-// part after the eigen-decomposition as one.  Taken when one workgroup per
-// matrix would leave most of the chip idle; UGLAD_WIDE_BWD=0 / 1 in the environment forces the choice for D > 128 (A/B, tests).
-static bool wide_wanted(int M, int D) {
-  if (D <= 128) return false;
-  int mode = g_wide_mode.load(std::memory_order_relaxed);
-  if (mode == -2) {  // unset: the environment decides, once -- and never over a value uglad_set_wide_mode() stored meanwhile
-    const char* e = std::getenv("UGLAD_WIDE_BWD");
-    const int env_mode = e ? (e[0] == '0' ? 0 : 1) : -1;
-    int expected = -2;
-    mode = g_wide_mode.compare_exchange_strong(expected, env_mode, std::memory_order_relaxed) ? env_mode : expected;
-  }
-  // measured (scripts/bench_bwd_wide.py): D = 256 wide wins at every batch size (82 vs 775 us at M = 1, 1.6 vs 2.1 ms at M = 512);
-  // D = 160: 70 vs 216 us at M = 8, 315 vs 273 us at M = 256
-  return mode >= 0 ? mode == 1 : (D > 192 || M <= 128);
-}
-
-// Few large matrices: the eigen-decomposition after the single-workgroup front (tridiagonalisation and merges below the last one have
-// run; reflectors in the slab R of each matrix): secular roots and eigenvector update of the last merge with many workgroups per
-// matrix (wide_fwd.h), back-transformation on two.  Leaves U in the matrix's second slab (row stride DP + 1) and the eigenvalues
-// in place of d in its (d, e, tau) record.
-static void launch_wide_eig_tail(float* workspace, const float* R, float* U_out, float* beta_out, int M, int D, hipStream_t st) {
-  const int DPr = padded_dim(D), ntp = wide_tiles(DPr), LD = DPr + 1;
-  const size_t rec = 3 * (size_t)DPr, slab = (size_t)big_floats_rt(DPr), lrec = (size_t)(DPr / 32) * 1024;
-  float* Tws = workspace + (size_t)M * 3 * DPr;
-  float* Q0 = workspace + (size_t)M * (3 * DPr + (DPr / 32) * 1024);  // eigenvectors before the last merge
-  float* Q1 = Q0 + slab / 2;                                            // ... after it, then back-transformed in place: U
-  hipLaunchKernelGGL(wide_secular_kernel, dim3((D + kWThreads / 8 - 1) / (kWThreads / 8), M), dim3(kWThreads), 0, st, Tws, lrec,
-                     workspace, rec, D, DPr);
-  hipLaunchKernelGGL(wide_merge_kernel, dim3(ntp, ntp, M), dim3(kWThreads), 0, st, (const float*)Q0, Q1, slab, (const float*)Tws,
-                     lrec, D, DPr, LD);
-  switch (DPr / 32) {
-#define UGLAD_BACK_CASE(K)                                                                                                   \
-  case K:                                                                                                                    \
-    hipLaunchKernelGGL((cell_fwd_back_kernel<K>), dim3((K * 2 + kWaves - 1) / kWaves, M), dim3(kThreads), 0, st,            \
-                       (const float*)workspace, Tws, R, U_out, beta_out, D, M);                                              \
-    break;
-#if UGLAD_MAX_NT >= 5 && UGLAD_HAS_NT(5)
-    UGLAD_BACK_CASE(5)
-#endif
-#if UGLAD_MAX_NT >= 6 && UGLAD_HAS_NT(6)
-    UGLAD_BACK_CASE(6)
-#endif
-#if UGLAD_MAX_NT >= 7 && UGLAD_HAS_NT(7)
-    UGLAD_BACK_CASE(7)
-#endif
-#if UGLAD_MAX_NT >= 8 && UGLAD_HAS_NT(8)
-    UGLAD_BACK_CASE(8)
-#endif
-#undef UGLAD_BACK_CASE
-    default: break;
-  }
-}
-
-// The same for a plain symmetric matrix whose tridiagonalisation has just been enqueued (LAUNCH_TRIDIAG(A, ..., out, workspace)), and
-// then out = (A + shift I)^-1 = U diag(1 / (beta + shift)) U^T with one Newton step, every product with one workgroup per 64 x 64 tile.
-// shift: device scalar per group with stride shift_stride floats, or nullptr.
-static void launch_wide_inverse(const float* A, const float* shift, int shift_stride, float* out, float* workspace, int M, int D,
-                                hipStream_t st) {
-  const int DPr = padded_dim(D), nt = wide_tiles(D), LD = DPr + 1, gs = group_size(M);
-  const size_t rec = 3 * (size_t)DPr, slab = (size_t)big_floats_rt(DPr), dd = (size_t)D * D;
-  float* Tws = workspace + (size_t)M * 3 * DPr;
-  float* Q0 = workspace + (size_t)M * (3 * DPr + (DPr / 32) * 1024);
-  float* Q1 = Q0 + slab / 2;
-  // front: everything below the last merge, one workgroup per matrix (the cell's kernel in its split mode; it only touches the
-  // workspace then, the other pointers just have to be valid)
-  DISPATCH_NT(D, hipLaunchKernelGGL((cell_fwd_lean_kernel<NT>), dim3(M), dim3(kThreads), 0, st, A, A, (const float*)workspace,
-                                    (const float*)workspace, out, (float*)nullptr, (float*)nullptr, (float*)nullptr, workspace,
-                                    (float*)nullptr, (const float*)workspace, Tws, D, UGLAD_SQRT_EXACT, gs, 2, LamStep{}));
-  launch_wide_eig_tail(workspace, out, nullptr, nullptr, M, D, st);
-  const WideFwd nofw{nullptr, nullptr, nullptr, nullptr};
-  const dim3 tiles(nt, nt, M), blk(kWThreads);
-  hipLaunchKernelGGL((wide_gemm_kernel<false, true, kEpiInverse>), tiles, blk, 0, st, (const float*)Q1, slab, (const float*)Q1, slab, Q0,
-                     slab, (const float*)nullptr, (const float*)workspace, shift, (float*)nullptr, rec, shift_stride, D, 0, gs, LD, LD,
-                     LD, nofw);  // X0 = U f U^T -> first slab
-  hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiResidual>), tiles, blk, 0, st, A, dd, (const float*)Q0, slab, Q1, slab,
-                     (const float*)nullptr, (const float*)nullptr, shift, (float*)nullptr, rec, shift_stride, D, 0, gs, D, LD, LD,
-                     nofw);  // E = I - (A + shift I) X0 -> second slab (U is dead)
-  hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiNewton>), tiles, blk, 0, st, (const float*)Q0, slab, (const float*)Q1, slab, out,
-                     dd, (const float*)nullptr, (const float*)nullptr, shift, (float*)nullptr, rec, shift_stride, D, 0, gs, LD, LD, D,
-                     nofw);  // out = X0 + X0 E
-}
-
-static int launch_cell_bwd_wide(const float* G_next, const float* S, const float* Z_in, const float* half, const float* U,
-                                const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
-                                float* glam_partial, float* workspace, int M, int D, int sqrt_mode, hipStream_t st) {
-  const int DP = padded_dim(D), nt = wide_tiles(D), nup = kWQ * (nt * (nt + 1) / 2), gs = group_size(M);  // nup: phase-A workgroups per matrix
-  const size_t pstride = 3 * (size_t)DP + (size_t)(DP / 32) * 1024;  // = kWsPerMatrix<DP>: the region the forward's d, e, tau, T factors use
-  const size_t slab = (size_t)big_floats_rt(DP), dd = (size_t)D * D;
-  float* part = workspace;
-  float* X0 = workspace + (size_t)M * pstride;
-  float* X1 = X0 + slab / 2;
-  const dim3 tiles(nt, nt, M), blk(kWThreads);
-  const WideFwd nofw{nullptr, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(wide_phase_a_kernel, dim3(nup, M), blk, 0, st, G_next, S, Z_in, half, params, X0, G_out, part, D, gs, slab,
-                     pstride);
-  hipLaunchKernelGGL((wide_gemm_kernel<true, false, kEpiStore>), tiles, blk, 0, st, U, dd, (const float*)X0, slab, X1, slab,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (size_t)0, 0, D, sqrt_mode,
-                     gs, D, D, D, nofw);  // R = U^T G_half
-  hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiDivDiff>), tiles, blk, 0, st, (const float*)X1, slab, U, dd, X0, slab,
-                     (const float*)nullptr, beta, lam, part, pstride, nup * kNRho, D, sqrt_mode, gs, D, D, D, nofw);  // Y = (R U) o F
-  hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiStore>), tiles, blk, 0, st, U, dd, (const float*)X0, slab, X1, slab,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (size_t)0, 0, D, sqrt_mode,
-                     gs, D, D, D, nofw);  // T2 = U Y
-  hipLaunchKernelGGL((wide_gemm_kernel<false, true, kEpiGout>), tiles, blk, 0, st, (const float*)X1, slab, U, dd, G_out, dd, S,
-                     (const float*)nullptr, lam, part, pstride, nup * kNRho + nt * nt, D, sqrt_mode, gs, D, D, D, nofw);  // G_out -= T2 U^T
-  hipLaunchKernelGGL(wide_reduce_kernel, dim3(M, kNRho + 1), dim3(64), 0, st, (const float*)part, pstride, grad_rho_partial, glam_partial, D);
-  return launch_status();
-}
-
-
-// ---- the matrix-iteration path (wide_ns.h): launch sequences
-static inline dim3 ns_ew_grid(int M, int D) {
-  const size_t dd = (size_t)D * D;
-  return dim3((unsigned)((dd + 255) / 256 < 256 ? (dd + 255) / 256 : 256), (unsigned)M);
-}
-// output tile of the products: 64 x 64, or 32 x 32 while the 64 x 64 tiles of the batch would not fill the 256 CUs (one 512 x 512
-// matrix: 64 workgroups; 45.8 vs 19.4 us per product, profiles/r03_ns_kernel_stats_d512_tile{64,32}.csv; the two tilings meet at 256
-// tiles of 64 x 64: D = 256 with 16 matrices 39.8 vs 39.1 ms per pass, D = 512 with 4: 66.2 vs 69.5, profiles/r03_ns_tile_probe.txt)
-static inline int ns_tile(int M, int D) {
-  if (const char* e = std::getenv("UGLAD_NS_TILE")) {  // (tests, A/B: read on every call)
-    if (e[0] == '3') return 32;
-    if (e[0] == '6') return 64;
-  }
-  return (long long)M * wide_tiles(D) * wide_tiles(D) < 256 ? 32 : 64;
-}
-static inline int ns_tiles_per_dim(int M, int D) { return ns_tile(M, D) == 32 ? (D + 31) / 32 : wide_tiles(D); }
-// one launch of up to three independent products C = alpha op(A) B + beta C + gamma I (fp64; ta: A is read transposed)
-struct NsLaunch {
-  NsBatch b{};
-  NsLaunch& add(const double* A, const double* B, double* C, double alpha, double beta, double gamma, bool ta = false) {
-    b.p[b.n++] = NsProd{A, B, C, alpha, beta, gamma, ta ? 1 : 0};
-    return *this;
-  }
-};
-static void ns_products(hipStream_t st, const NsLayout& l, int M, int D, const NsLaunch& nl, const float* gamma_div = nullptr, bool frob = false) {
-  NsEpi ep{};
-  ep.gamma_div = gamma_div;
-  ep.hdr = frob ? l.H : nullptr;
-  ep.hdr_stride = l.hdr;
-  ep.gs = group_size(M);
-  // (the tiling follows the batch alone, not the products per launch: per-tile sums and their readers agree on it)
-  if (ns_tile(M, D) == 32) {
-    const int n32 = (D + 31) / 32;
-    if (ns_prefetch_all(D))
-      hipLaunchKernelGGL((ns_gemm64_kernel<kNsAffine, 32, true>), dim3(n32, n32, M * nl.b.n), dim3(kWThreads), 0, st, nl.b, l.dregion, D, ep);
-    else
-      hipLaunchKernelGGL((ns_gemm64_kernel<kNsAffine, 32>), dim3(n32, n32, M * nl.b.n), dim3(kWThreads), 0, st, nl.b, l.dregion, D, ep);
-  } else {
-    const int nt = wide_tiles(D);
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsAffine, 64>), dim3(nt, nt, M * nl.b.n), dim3(kWThreads), 0, st, nl.b, l.dregion, D, ep);
-  }
-}
-
-static int launch_cell_fwd_ns(const float* S, const float* Z_in, const float* lam, const float* params, float* Z_out, float* half_out,
-                              float* sqrt_out, float* normF_partial, float* cond_max, float* workspace, int M, int D, hipStream_t st) {
-  const NsLayout l = ns_layout(workspace, M, D);
-  const int nt = wide_tiles(D), gs = group_size(M);
-  double* Wb = l.Wd;                  // b
-  double* Wy = l.Wd + 1 * l.dslab;    // A -> Y
-  double* Wt = l.Wd + 2 * l.dslab;    // T
-  double* Wz = l.Wd + 3 * l.dslab;    // Z
-  double* Wy2 = l.Wd + 4 * l.dslab;   // the next Y
-  double* Wz2 = l.Wd + 5 * l.dslab;   // the next Z
-  const dim3 ew = ns_ew_grid(M, D);
-  hipLaunchKernelGGL(ns_b_kernel, ew, dim3(256), 0, st, S, Z_in, lam, Wb, l.dregion, D, gs);
-  ns_products(st, l, M, D, NsLaunch().add(Wb, Wb, Wy, 1.0, 0.0, 4.0, true), lam, true);  // A = b^T b + 4/lam I, ||A||_F^2 per tile
-  if (cond_max) hipLaunchKernelGGL(ns_cond_kernel, dim3(nt, M), dim3(256), 0, st, (const double*)Wy, l.dregion, l.H, l.hdr, D);
-  const int ntd = ns_tiles_per_dim(M, D);
-  hipLaunchKernelGGL(ns_norm_kernel, dim3(M), dim3(64), 0, st, l.H, l.hdr, lam, cond_max, D, gs, ntd * ntd);
-  hipLaunchKernelGGL(ns_start_kernel, ew, dim3(256), 0, st, Wy, Wt, Wz, l.dregion, (const float*)l.H, l.hdr, D);
-  ns_products(st, l, M, D, NsLaunch().add(Wy, Wt, Wy2, 1.0, 0.0, 0.0));  // Y1 = Y0 T0  (Z1 = T0 is in place)
-  double *Y = Wy2, *Yn = Wy, *Z = Wz, *Zn = Wz2;
-  for (int t = 1; t < kNsIters; ++t) {
-    ns_products(st, l, M, D, NsLaunch().add(Z, Y, Wt, -0.5, 0.0, 1.5));  // T = (3 I - Z Y) / 2
-    if (t + 1 < kNsIters) {
-      ns_products(st, l, M, D, NsLaunch().add(Y, Wt, Yn, 1.0, 0.0, 0.0).add(Wt, Z, Zn, 1.0, 0.0, 0.0));  // Y <- Y T ; Z <- T Z
-      double* t0 = Y; Y = Yn; Yn = t0;
-      t0 = Z; Z = Zn; Zn = t0;
-    }
-  }
-  // the last Y T: theta_half = (sqrt(||A||_F) Y T - b) / 2, rhoNN + threshold, the norm -- upper tiles, mirrored
-  NsEpi ep{};
-  ep.hdr = l.H;
-  ep.hdr_stride = l.hdr;
-  ep.gs = gs;
-  ep.b = Wb;
-  ep.S = S;
-  ep.Zin = Z_in;
-  ep.params = params;
-  ep.lam = lam;
-  ep.Zout = Z_out;
-  ep.half_out = half_out;
-  ep.sqrt_out = sqrt_out;
-  const NsLaunch last = NsLaunch().add(Y, Wt, nullptr, 1.0, 0.0, 0.0);
-  if (ns_tile(M, D) == 32 && ns_prefetch_all(D))
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsTheta, 32, true>), dim3(ntd, ntd, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  else if (ns_tile(M, D) == 32)
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsTheta, 32>), dim3(ntd, ntd, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  else
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsTheta, 64>), dim3(nt, nt, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  hipLaunchKernelGGL(ns_norm_reduce_kernel, dim3(M), dim3(64), 0, st, (const float*)l.H, l.hdr, ntd, normF_partial, D);
-  return launch_status();
-}
-
-static int launch_cell_bwd_ns(const float* G_next, const float* S, const float* Z_in, const float* half, const float* sqrtm,
-                              const float* lam, const float* params, float* G_out, float* grad_rho_partial, float* glam_partial,
-                              float* workspace, int M, int D, hipStream_t st) {
-  const NsLayout l = ns_layout(workspace, M, D);
-  const int nt = wide_tiles(D), nup = kWQ * (nt * (nt + 1) / 2), gs = group_size(M);
-  double* Wb = l.Wd;                  // b
-  double* Wa = l.Wd + 1 * l.dslab;    // A
-  double* Wp = l.Wd + 2 * l.dslab;    // P
-  double* Wq = l.Wd + 3 * l.dslab;    // Q
-  double* Wr = l.Wd + 4 * l.dslab;    // R, then Q + Q^T
-  double* Wa2 = l.Wd + 5 * l.dslab;   // the next A
-  double* Wq2 = l.Wd + 6 * l.dslab;   // the next Q
-  const dim3 ew = ns_ew_grid(M, D);
-  hipLaunchKernelGGL(wide_phase_a_kernel, dim3(nup, M), dim3(kWThreads), 0, st, G_next, S, Z_in, half, params, l.Gh, G_out, l.H, D, gs, l.region,
-                     l.hdr);
-  hipLaunchKernelGGL(ns_b_kernel, ew, dim3(256), 0, st, S, Z_in, lam, Wb, l.dregion, D, gs);
-  hipLaunchKernelGGL(ns_frob_kernel, dim3(kNsFrobBlocks, M), dim3(256), 0, st, sqrtm, (size_t)D * D, l.H, l.hdr, D);
-  hipLaunchKernelGGL(ns_bwd_start_kernel, ew, dim3(256), 0, st, sqrtm, (const float*)l.Gh, l.region, Wa, Wq, l.dregion, (const float*)l.H, l.hdr,
-                     D);
-  double *A = Wa, *An = Wa2, *Q = Wq, *Qn = Wq2;
-  for (int t = 0; t < kNsIters; ++t) {  // torch_sqrtm.py:42-44, three launches per step
-    const bool more = t + 1 < kNsIters;
-    ns_products(st, l, M, D, NsLaunch().add(A, A, Wp, -1.0, 0.0, 3.0).add(A, Q, Wr, 1.0, 0.0, 0.0, true));  // P = 3 I - A A ; R = A^T Q ...
-    NsLaunch second;
-    second.add(Q, A, Wr, -1.0, 1.0, 0.0).add(Q, Wp, Qn, 1.0, 0.0, 0.0);  // ... - Q A ; Q' = Q P ...
-    if (more) second.add(A, Wp, An, 0.5, 0.0, 0.0);                       // A <- A P / 2
-    ns_products(st, l, M, D, second);
-    ns_products(st, l, M, D, NsLaunch().add(A, Wr, Qn, -0.5, 0.5, 0.0, true));  // ... - A^T R, halved
-    if (more) {
-      double* t0 = A; A = An; An = t0;
-    }
-    double* t0 = Q; Q = Qn; Qn = t0;
-  }
-  hipLaunchKernelGGL(ns_symm_kernel, ew, dim3(256), 0, st, (const double*)Q, Wr, l.dregion, D);
-  NsEpi ep{};
-  ep.hdr = l.H;
-  ep.hdr_stride = l.hdr;
-  ep.gs = gs;
-  ep.S = S;
-  ep.lam = lam;
-  ep.Zout = G_out;
-  ep.Gh = l.Gh;
-  ep.gh_stride = l.region;
-  const int ntd = ns_tiles_per_dim(M, D);
-  const NsLaunch last = NsLaunch().add(Wb, Wr, nullptr, 1.0, 0.0, 0.0);
-  if (ns_tile(M, D) == 32 && ns_prefetch_all(D))
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsGout, 32, true>), dim3(ntd, ntd, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  else if (ns_tile(M, D) == 32)
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsGout, 32>), dim3(ntd, ntd, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  else
-    hipLaunchKernelGGL((ns_gemm64_kernel<kNsGout, 64>), dim3(nt, nt, M), dim3(kWThreads), 0, st, last.b, l.dregion, D, ep);
-  hipLaunchKernelGGL(ns_glam_kernel, dim3(M), dim3(64), 0, st, l.H, l.hdr, ntd * ntd, nup * kNRho, D);
-  hipLaunchKernelGGL(wide_reduce_kernel, dim3(M, kNRho + 1), dim3(64), 0, st, (const float*)l.H, l.hdr, grad_rho_partial, glam_partial, D);
-  return launch_status();
-}
-
-// out = (A + shift I)^-1 (and log det in the header) beyond the eigensolver's size: L D L^T of the padded matrix, one Newton step
-static void launch_ns_inverse(const float* A, const float* shift, int shift_stride, float* out, float* logdet_out, float* workspace, int M, int D,
-                              hipStream_t st) {
-  const NsLayout l = ns_layout(workspace, M, D);
-  const int nt = wide_tiles(D), gs = group_size(M), FD = ns_fact_dim(D), LDc = FD + 1;
-  float* X1 = l.W;                                           // the factorisation's first slab, dead once it returns (row stride 513)
-  float* X0 = l.W + 2 * (size_t)FD * (FD + 1);     // (row stride FD + 1)
-  float* E = l.W + 3 * (size_t)FD * (FD + 1);      // residual, row stride D
-  // the factorisation: ONE workgroup per matrix up to D = 256 (0.35 ms there), a sequence of launches with the tiles of every phase spread
-  // over the chip beyond (ns_ldl_phase_kernel: 5 nt + 1 launches, nt = ceil(D / 32); UGLAD_LDL_LAUNCHES=0 / 1 in the environment forces one or the other)
-  const char* ldl_env = std::getenv("UGLAD_LDL_LAUNCHES");  // (read on every call: tests flip it)
-  const int forced = ldl_env ? (ldl_env[0] == '0' ? 0 : 1) : -1;
-  const int ntl = (D + 31) / 32;
-  const bool phases = forced >= 0 ? forced == 1 : ntl >= 9;
-  if (!phases) {
-    if (FD == kNsFactSmall)
-      hipLaunchKernelGGL(ns_ldl_kernel<kNsFactSmall>, dim3(M), dim3(64 * kNsLdlWaves), 0, st, A, shift, shift_stride, l.W, l.region, logdet_out, D, gs);
-    else
-      hipLaunchKernelGGL(ns_ldl_kernel<kNsMaxD>, dim3(M), dim3(64 * kNsLdlWaves), 0, st, A, shift, shift_stride, l.W, l.region, logdet_out, D, gs);
-  } else {
-    auto phase = [&](int ph, int jd, int items) {  // `items` tiles (one wave each) or elements (one thread each, capped) of work per matrix
-      int wgs = 1;
-      if (ph == kLdlInit || ph == kLdlScale || ph == kLdlFinish) {
-        wgs = (items + 64 * kLdlWavesPerWg - 1) / (64 * kLdlWavesPerWg);
-        if (wgs > 512) wgs = 512;
-      } else {
-        wgs = (items + kLdlWavesPerWg - 1) / kLdlWavesPerWg;
-      }
-      if (wgs < 1) wgs = 1;
-      if (FD == kNsFactSmall)
-        hipLaunchKernelGGL(ns_ldl_phase_kernel<kNsFactSmall>, dim3(wgs, M), dim3(64 * kLdlWavesPerWg), 0, st, ph, jd, A, shift, shift_stride, l.W, l.region,
-                           logdet_out, D, gs);
-      else
-        hipLaunchKernelGGL(ns_ldl_phase_kernel<kNsMaxD>, dim3(wgs, M), dim3(64 * kLdlWavesPerWg), 0, st, ph, jd, A, shift, shift_stride, l.W, l.region,
-                           logdet_out, D, gs);
-    };
-    const int dpl = ntl * 32;
-    phase(kLdlInit, 0, dpl * dpl);
-    for (int j = 0; j < ntl; ++j) {
-      phase(kLdlDiag, j, 1);
-      if (j + 1 < ntl) {
-        phase(kLdlPanel, j, ntl - 1 - j);
-        phase(kLdlTrail, j, (ntl - 1 - j) * (ntl - j) / 2);
-      }
-    }
-    for (int d = 1; d < ntl; ++d) {
-      phase(kLdlWSum, d, ntl - d);
-      phase(kLdlWMul, d, ntl - d);
-    }
-    phase(kLdlScale, 0, dpl * dpl);
-    phase(kLdlX, 0, ntl * (ntl + 1) / 2);
-    phase(kLdlFinish, 0, dpl * dpl);
-  }
-  const WideFwd nofw{};
-  const dim3 tiles(nt, nt, M), blk(kWThreads);
-  // two Newton steps X <- X + X (I - A X): without pivoting the factorisation of a strongly indefinite matrix is only a starting point
-  // (the reference's Theta_L at D = 512, cond 2e5 with 104 negative eigenvalues: 4e-2 -> 1.8e-3 -> the ~2e-4 of a pivoted LU in fp32)
-  for (int step = 0; step < 2; ++step) {
-    const float* Xin = step ? X1 : X0;
-    float* Xout = step ? out : X1;
-    hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiResidual>), tiles, blk, 0, st, A, (size_t)D * D, Xin, l.region, E, l.region,
-                       (const float*)nullptr, (const float*)nullptr, shift, (float*)nullptr, l.hdr, shift_stride, D, 0, gs, D, LDc, D, nofw);
-    hipLaunchKernelGGL((wide_gemm_kernel<false, false, kEpiNewton>), tiles, blk, 0, st, Xin, l.region, (const float*)E, l.region, Xout,
-                       step ? (size_t)D * D : l.region, (const float*)nullptr, (const float*)nullptr, shift, (float*)nullptr, l.hdr,
-                       shift_stride, D, 0, gs, LDc, D, step ? D : LDc, nofw);
-  }
-}
-
-// second launch of the forward cell: the lean kernel (eig_lean.h) -- its one big matrix in LDS up to D = 128 (two workgroups
-// per CU), in a workspace slab beyond.
-static int launch_cell_stage2(const float* S, const float* Z_in, const float* lam, const float* params, float* Z_out,
-                              float* half_out, float* U_out, float* beta_out, float* normF_partial, float* cond_max,
-                              float* workspace, int M, int D, int sqrt_mode, hipStream_t st, LamStep ls = LamStep{}) {
-  const int DPr = padded_dim(D);
-  float* Tws = workspace + (size_t)M * 3 * DPr;
-  {
-    // few large matrices (wide_bwd.h, wide_fwd.h): the single-workgroup kernel stops before the last merge of the divide & conquer
-    // (D > 128: there is one); secular roots, eigenvector update, back-transformation and theta_half follow as their own launches
-    const int split = wide_wanted(M, D) ? 2 : 0;
-    DISPATCH_NT(D, hipLaunchKernelGGL((cell_fwd_lean_kernel<NT>), dim3(M), dim3(kThreads), 0, st, S, Z_in, lam, params, Z_out,
-                                      half_out, U_out, beta_out, normF_partial, cond_max, workspace, Tws, D, sqrt_mode, group_size(M), split,
-                                      split ? LamStep{} : ls));
-    if (split) {
-      const int nt = wide_tiles(D), LD = DPr + 1;
-      const size_t rec = 3 * (size_t)DPr, slab = (size_t)big_floats_rt(DPr);
-      float* Q1 = workspace + (size_t)M * (3 * DPr + (DPr / 32) * 1024) + slab / 2;  // U, row stride DP + 1
-      launch_wide_eig_tail(workspace, Z_out, U_out, beta_out, M, D, st);
-      // theta_half = (U phi) U^T, rhoNN + threshold and the norm with one workgroup per upper 64 x 64 tile (wide_bwd.h)
-      WideFwd fw{Z_in, params, half_out, cond_max};
-      hipLaunchKernelGGL((wide_gemm_kernel<false, true, kEpiThetaHalf>), dim3(nt, nt, M), dim3(kWThreads), 0, st, (const float*)Q1, slab,
-                         (const float*)Q1, slab, Z_out, (size_t)D * D, S, (const float*)workspace, lam, workspace, rec, DPr, D, sqrt_mode,
-                         group_size(M), LD, LD, D, fw);
-      hipLaunchKernelGGL(wide_norm_reduce_kernel, dim3((M + 63) / 64), dim3(64), 0, st, (const float*)workspace, rec, DPr,
-                         normF_partial, M, D);
-    }
-  }
-  return launch_status();
-}
-
-int uglad_cell_fwd(const float* S, const float* Z_in, const float* lam, const float* params, float* Z_out,
-                   float* half_out, float* U_out, float* beta_out, float* normF_partial, float* cond_max, float* workspace, int M,
-                   int D, int sqrt_mode, uglad_stream_t stream) {
-  if (!S || !Z_in || !lam || !params || !Z_out || !normF_partial || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-  hipStream_t st = (hipStream_t)stream;
-  if (ns_path(M, D, half_out != nullptr || U_out != nullptr, sqrt_mode)) {
-    if (sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;  // (the iteration IS the ten-step square root)
-    return launch_cell_fwd_ns(S, Z_in, lam, params, Z_out, half_out, U_out, normF_partial, cond_max, workspace, M, D, st);
-  }
-  LAUNCH_TRIDIAG(S, Z_in, lam, Z_out, workspace);
-  return launch_cell_stage2(S, Z_in, lam, params, Z_out, half_out, U_out, beta_out, normF_partial, cond_max, workspace, M, D, sqrt_mode,
-                            st);
-}
-
-int uglad_cell_fwd_stage2(const float* S, const float* Z_in, const float* lam, const float* params, float* Z_out,
-                          float* half_out, float* U_out, float* beta_out, float* normF_partial, float* cond_max, float* workspace,
-                          int M, int D, int sqrt_mode, uglad_stream_t stream) {
-  if (!S || !Z_in || !lam || !params || !Z_out || !normF_partial || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-  if (ns_wanted(D)) return UGLAD_E_DIM;  // (no tridiagonal stage to follow on the matrix-iteration path: uglad_cell_fwd is one piece there)
-  return launch_cell_stage2(S, Z_in, lam, params, Z_out, half_out, U_out, beta_out, normF_partial, cond_max, workspace, M, D,
-                            sqrt_mode, (hipStream_t)stream);
-}
-
-int uglad_sum_partials(const float* partials, int n, float* out, uglad_stream_t stream) {
-  if (!partials || !out) return UGLAD_E_NULL;
-  if (n < 1) return UGLAD_E_DIM;
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(t_groups), dim3(kThreads), 0, (hipStream_t)stream, partials, group_size(n), out);
-  return launch_status();
-}
-
-int uglad_lambda_step(const float* normF_sum, float inv_M, const float* lam_prev, const float* params, float* lam_next,
-                      float* lam_in_next, uglad_stream_t stream) {
-  if (!normF_sum || !lam_prev || !params || !lam_next || !lam_in_next) return UGLAD_E_NULL;
-  hipLaunchKernelGGL(lambda_step_kernel, dim3((t_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream, normF_sum, inv_M,
-                     lam_prev, params, lam_next, lam_in_next, t_groups);
-  return launch_status();
-}
-
-int uglad_cell_bwd(const float* G_next, const float* S, const float* Z_in, const float* half, const float* U,
-                   const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
-                   float* glam_partial, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream) {
-  if (!G_next || !S || !Z_in || !half || !U || !beta || !lam || !params || !G_out || !grad_rho_partial || !glam_partial ||
-      (D > 128 && !workspace))
-    return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-  hipStream_t st = (hipStream_t)stream;
-  if (ns_path(M, D, true, sqrt_mode)) {  // (as the forward call that saved this step's state)
-    if (sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-    return launch_cell_bwd_ns(G_next, S, Z_in, half, U, lam, params, G_out, grad_rho_partial, glam_partial, workspace, M, D, st);
-  }
-  if (wide_wanted(M, D)) return launch_cell_bwd_wide(G_next, S, Z_in, half, U, beta, lam, params, G_out, grad_rho_partial,
-                                                          glam_partial, workspace, M, D, sqrt_mode, st);
-  DISPATCH_NT(D, hipLaunchKernelGGL((cell_bwd_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_next, S, Z_in, half, U, beta,
-                                    lam, params, G_out, grad_rho_partial, glam_partial, workspace, D, sqrt_mode, group_size(M), 1, 0));
-  return launch_status();
-}
-
-// Steps L-1 .. 0 of the backward pass in one launch (D <= 128, one workgroup per matrix): dL/dZ never leaves LDS between the steps.
-// All arrays are the whole-pass ones (step-major, as uglad_glad_backward takes them); G_out receives dL/dZ_0.
-static int launch_cell_bwd_all_steps(const float* G_L, const float* S, const float* Z, const float* half, const float* U,
-                                     const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
-                                     float* glam_partial, int L, int M, int D, int sqrt_mode, hipStream_t st, float* gS = nullptr) {
-  const size_t mdd = (size_t)M * D * D, last = (size_t)(L - 1);
-  if (gS) {
-    DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((cell_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_L, S, Z + last * mdd,
-                                            half + last * mdd, U + last * mdd, beta + last * M * D, lam + last * t_groups, params, G_out,
-                                            grad_rho_partial, glam_partial + last * M, nullptr, D, sqrt_mode, group_size(M), L, t_groups,
-                                            gS));
-    return launch_status();
-  }
-  DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((cell_bwd_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_L, S, Z + last * mdd, half + last * mdd,
-                                          U + last * mdd, beta + last * M * D, lam + last * t_groups, params, G_out, grad_rho_partial,
-                                          glam_partial + last * M, nullptr, D, sqrt_mode, group_size(M), L, t_groups));
-  return launch_status();
-}
-
-// One step of the backward pass that also accumulates dL/dS into gS: the spectral path's one-workgroup cell (uglad_cell_bwd's last case;
-// uglad_glad_backward_wrt_s has refused the passes that take its other two paths).
-static int launch_cell_bwd_step_gs(const float* G_next, const float* S, const float* Z_in, const float* half, const float* U,
-                                   const float* beta, const float* lam, const float* params, float* G_out, float* grad_rho_partial,
-                                   float* glam_partial, float* workspace, int M, int D, int sqrt_mode, float* gS, hipStream_t st) {
-  DISPATCH_NT(D, hipLaunchKernelGGL((cell_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, G_next, S, Z_in, half, U, beta, lam, params,
-                                    G_out, grad_rho_partial, glam_partial, workspace, D, sqrt_mode, group_size(M), 1, 0, gS));
-  return launch_status();
-}
-
-int uglad_loss_fwd(const float* theta, const float* S, int s_batch, const float* struct_theta, float* loss_partial,
-                   float* theta_inv_out, float* workspace, int M, int D, uglad_stream_t stream) {
-  if (!theta || !S || !loss_partial || !theta_inv_out || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (s_batch != 1 && s_batch != M) return UGLAD_E_DIM;
-  hipStream_t st = (hipStream_t)stream;
-  if (ns_factorisation(M, D)) {
-    const NsLayout l = ns_layout(workspace, M, D);
-    launch_ns_inverse(theta, nullptr, 0, theta_inv_out, loss_partial, workspace, M, D, st);  // (log det parked in loss_partial)
-    hipLaunchKernelGGL(wide_loss_trace_kernel, dim3(wide_tiles(D), M), dim3(kWThreads), 0, st, theta, S, s_batch, struct_theta, l.H, l.hdr,
-                       ns_off_tiles(D), D);
-    hipLaunchKernelGGL(ns_loss_finish_kernel, dim3((M + 63) / 64), dim3(64), 0, st, (const float*)l.H, l.hdr, ns_off_tiles(D),
-                       (const float*)loss_partial, loss_partial, M, D);
-    return launch_status();
-  }
-  const int* only = nullptr;
-  if (D <= 128 && cholesky_enabled()) {
-    int* flags = chol_flags(workspace, M, D);
-    DISPATCH_NT_SMALL(D, hipLaunchKernelGGL((chol_loss_kernel<NT>), dim3(M), dim3(kThreads), 0, st, theta, S, s_batch, struct_theta,
-                                            loss_partial, theta_inv_out, flags, D));
-    only = flags;
-  }
-  LAUNCH_TRIDIAG_IF(theta, (const float*)nullptr, (const float*)nullptr, theta_inv_out, workspace, only);
-  if (wide_wanted(M, D)) {
-    const int DPr = padded_dim(D);
-    launch_wide_inverse(theta, nullptr, 0, theta_inv_out, workspace, M, D, st);
-    hipLaunchKernelGGL(wide_loss_trace_kernel, dim3(wide_tiles(D), M), dim3(kWThreads), 0, st, theta, S, s_batch, struct_theta, workspace,
-                       3 * (size_t)DPr, DPr, D);
-    hipLaunchKernelGGL(wide_loss_finish_kernel, dim3((M + 63) / 64), dim3(64), 0, st, (const float*)workspace, 3 * (size_t)DPr, DPr,
-                       loss_partial, M, D);
-    return launch_status();
-  }
-  DISPATCH_NT(D, hipLaunchKernelGGL((loss_fwd_kernel<NT>), dim3(M), dim3(kThreads), 0, st, theta, S, s_batch, struct_theta,
-                                    loss_partial, theta_inv_out, workspace, D, only));
-  return launch_status();
-}
-
-int uglad_loss_bwd(const float* theta, const float* theta_inv, const float* S, int s_batch, const float* struct_theta,
-                   const float* g_up, float scale, float* G_out, int M, int D, uglad_stream_t stream) {
-  if (!theta || !theta_inv || !S || !g_up || !G_out) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (s_batch != 1 && s_batch != M) return UGLAD_E_DIM;
-  const size_t total = (size_t)M * D * D;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, theta, theta_inv, S, s_batch,
-                     struct_theta, g_up, scale, G_out, D, total);
-  return launch_status();
-}
-
-int uglad_loss_bwd_wrt_s(const float* theta, const float* theta_inv, const float* S, int s_batch, const float* struct_theta,
-                         const float* g_up, float scale, float* G_out, float* gS, int M, int D, uglad_stream_t stream) {
-  if (!gS) return UGLAD_E_NULL;
-  int rc = uglad_loss_bwd(theta, theta_inv, S, s_batch, struct_theta, g_up, scale, G_out, M, D, stream);
-  if (rc) return rc;
-  const size_t total = (size_t)s_batch * D * D;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(loss_bwd_gs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, theta, g_up, scale, gS, s_batch, M, D);
-  return launch_status();
-}
-
-int uglad_finish_grads(const float* gt_partial, const float* grad_rho_partial, const float* glam_partial,
-                       const float* lam_in, const float* params, float* grad, int L, int M, uglad_stream_t stream) {
-  if (!gt_partial || !grad_rho_partial || !glam_partial || !lam_in || !params || !grad) return UGLAD_E_NULL;
-  if (L < 1 || M < 1) return UGLAD_E_DIM;
-  hipLaunchKernelGGL(finish_grads_kernel, dim3(t_groups), dim3(kThreads), 0, (hipStream_t)stream, gt_partial, grad_rho_partial,
-                     glam_partial, lam_in, params, grad, L, M, group_size(M));
-  return launch_status();
-}
-
-// Zero n floats with a kernel, not hipMemsetAsync: captured into a caller's graph (PyTorch's stream capture, ROCm 7.2) the memset NODES of the two
-// small zero-fills of a pass did not replay as zero-fills -- the 4-byte one left 5e36 behind, the 112-byte one left every other float
-// unzeroed (tests/test_gpu_parity.py::test_a_whole_pass_can_be_captured_into_the_callers_graph failed on exactly these two buffers) --
-// while a kernel node replays as launched.
-static int zero_floats(float* p, size_t n, hipStream_t st) {
-  const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-  hipLaunchKernelGGL(zero_kernel, dim3(grid), dim3(256), 0, st, p, n);
-  return launch_status();
-}
-
-// ---- the whole unrolled pass in one call (single-process case: no collective between the norm and the lambda step)
-static int enqueue_glad_forward(const float* S, const float* params, float lambda_init, int init_diag, int L, float* Z,
-                                int z_slabs, float* half, float* U, float* beta, float* lam, float* lam_in, float* nf_partial,
-                                float* nf_sum, float* cond_max, float* workspace, int M, int D, int sqrt_mode,
-                                uglad_stream_t stream, int m_global = 0, uglad_allreduce_fn exchange = nullptr,
-                                void* exchange_ctx = nullptr) {
-  if (!S || !params || !Z || !lam || !lam_in || !nf_partial || !nf_sum || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (L < 1 || z_slabs < 2) return UGLAD_E_DIM;
-  const size_t mdd = (size_t)M * D * D;
-  int rc = uglad_init_theta(S, params, init_diag, Z, workspace, M, D, stream);
-  if (rc) return rc;
-  if (cond_max) {  // running maximum over the L steps: starts at 0
-    if ((rc = zero_floats(cond_max, (size_t)M, (hipStream_t)stream))) return rc;
-  }
-  if ((rc = uglad_lambda_init(params, lambda_init, lam, lam_in, stream))) return rc;
-  const int G = t_groups;  // lam: (L + 1, G), lam_in: (L + 1, G, 2), nf_sum: (G)
-  const float inv_m = 1.0f / (float)(exchange ? m_global : group_size(M));
-  // one matrix per group on the eigensolver's one-workgroup kernel: the lambda step rides in the cell's second launch (LamStep)
-  const bool fuse_lambda = !exchange && group_size(M) == 1 && D <= UGLAD_MAX_EIG_DIM && !wide_wanted(M, D) &&
-                           !ns_path(M, D, half != nullptr || U != nullptr, sqrt_mode) && !std::getenv("UGLAD_NO_FUSED_LAMBDA");
-  for (int k = 0; k < L; ++k) {
-    const float* zi = Z + (size_t)(k % z_slabs) * mdd;
-    float* zo = Z + (size_t)((k + 1) % z_slabs) * mdd;
-    if (fuse_lambda) {
-      if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-      hipStream_t st = (hipStream_t)stream;
-      const float* lamk = lam + (size_t)k * G;
-      LAUNCH_TRIDIAG(S, zi, lamk, zo, workspace);
-      const LamStep ls{nf_sum, lam + (size_t)(k + 1) * G, lam_in + 2 * (size_t)(k + 1) * G, inv_m};
-      if ((rc = launch_cell_stage2(S, zi, lamk, params, zo, half ? half + (size_t)k * mdd : nullptr, U ? U + (size_t)k * mdd : nullptr,
-                                   beta ? beta + (size_t)k * M * D : nullptr, nf_partial, cond_max, workspace, M, D, sqrt_mode, st, ls)))
-        return rc;
-      continue;
-    }
-    rc = uglad_cell_fwd(S, zi, lam + (size_t)k * G, params, zo, half ? half + (size_t)k * mdd : nullptr,
-                        U ? U + (size_t)k * mdd : nullptr, beta ? beta + (size_t)k * M * D : nullptr, nf_partial, cond_max, workspace,
-                        M, D, sqrt_mode, stream);
-    if (rc) return rc;
-    if (exchange) {
-      // sharded batch: local sum -> SUM over the ranks (stream-ordered, no host decision) -> LambdaNN on every rank from the same bits
-      if ((rc = uglad_sum_partials(nf_partial, M, nf_sum, stream))) return rc;
-      if ((rc = exchange(nf_sum, 1, exchange_ctx, stream))) return rc;
-      if ((rc = uglad_lambda_step(nf_sum, inv_m, lam + k, params, lam + k + 1, lam_in + 2 * (size_t)(k + 1), stream))) return rc;
-      continue;
-    }
-    // (uglad_sum_partials + uglad_lambda_step as one launch: nothing is exchanged between them in a single-process pass)
-    hipLaunchKernelGGL(norm_lambda_kernel, dim3(G), dim3(kThreads), 0, (hipStream_t)stream, nf_partial, group_size(M), inv_m,
-                       lam + (size_t)k * G, params, nf_sum, lam + (size_t)(k + 1) * G, lam_in + 2 * (size_t)(k + 1) * G);
-    if ((rc = launch_status())) return rc;
-  }
-  return 0;
-}
-
-static int enqueue_glad_backward(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
-                                 const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
-                                 float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
-                                 float* grad, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream,
-                                 float* gS = nullptr) {
-  if (!G_L || !S || !params || !Z || !half || !U || !beta || !lam || !lam_in || !gbuf0 || !gbuf1 || !grad_rho_partial ||
-      !glam_partial || !gt_partial || !grad)
-    return UGLAD_E_NULL;
-  CHECK_DIMS(M, D);
-  if (L < 1) return UGLAD_E_DIM;
-  const size_t mdd = (size_t)M * D * D;
-  int rc = zero_floats(grad_rho_partial, (size_t)M * UGLAD_NRHO, (hipStream_t)stream);
-  if (rc) return rc;
-  if (gS && (rc = zero_floats(gS, mdd, (hipStream_t)stream))) return rc;
-  const float* cur = G_L;
-  if (D <= 128 && !ns_wanted(D) && !wide_wanted(M, D) && persistent_bwd_enabled()) {
-    if ((rc = launch_cell_bwd_all_steps(G_L, S, Z, half, U, beta, lam, params, gbuf0, grad_rho_partial, glam_partial, L, M, D, sqrt_mode,
-                                        (hipStream_t)stream, gS)))
-      return rc;
-    cur = gbuf0;
-  } else
-  for (int k = L - 1; k >= 0; --k) {
-    float* out = (k & 1) ? gbuf1 : gbuf0;
-    if (gS && (ns_path(M, D, true, sqrt_mode) || wide_wanted(M, D))) {  // no dL/dS variant there: the step as it is, then its dL/dS
-      rc = uglad_cell_bwd(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
-                          lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M, D,
-                          sqrt_mode, stream);
-      if (rc) return rc;
-      const int grid = (int)((mdd + 255) / 256 < 4096 ? (mdd + 255) / 256 : 4096);
-      hipLaunchKernelGGL(cell_gs_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, cur, S, Z + (size_t)k * mdd,
-                         half + (size_t)k * mdd, lam + (size_t)k * t_groups, params, (const float*)out, gS, D, group_size(M), mdd);
-      rc = launch_status();
-    } else if (gS)
-      rc = launch_cell_bwd_step_gs(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
-                                   lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M,
-                                   D, sqrt_mode, gS, (hipStream_t)stream);
-    else
-      rc = uglad_cell_bwd(cur, S, Z + (size_t)k * mdd, half + (size_t)k * mdd, U + (size_t)k * mdd, beta + (size_t)k * M * D,
-                          lam + (size_t)k * t_groups, params, out, grad_rho_partial, glam_partial + (size_t)k * M, workspace, M, D,
-                          sqrt_mode, stream);
-    if (rc) return rc;
-    cur = out;
-  }
-  if ((rc = uglad_init_theta_bwd(Z, cur, init_diag, gt_partial, workspace, M, D, stream))) return rc;
-  if (gS) {  // the Theta_0 term of dL/dS
-    hipStream_t st = (hipStream_t)stream;
-    if (init_diag == 1) {
-      const size_t total = (size_t)M * D;
-      const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-      hipLaunchKernelGGL(init_bwd_diag_gs_kernel, dim3(grid), dim3(256), 0, st, (const float*)Z, cur, gS, D, total);
-    } else if (ns_factorisation(M, D)) {  // beyond the one-workgroup kernels: T = Theta0 G0 into the idle G buffer, R = T Theta0 into G0's
-      float* T = (cur == gbuf0) ? gbuf1 : gbuf0;
-      float* R = const_cast<float*>(cur);
-      const dim3 tiles((D + 63) / 64, (D + 63) / 64, M);
-      hipLaunchKernelGGL(gs_gemm_kernel, tiles, dim3(256), 0, st, (const float*)Z, cur, T, D);
-      hipLaunchKernelGGL(gs_gemm_kernel, tiles, dim3(256), 0, st, (const float*)T, (const float*)Z, R, D);
-      const int grid = (int)((mdd + 255) / 256 < 4096 ? (mdd + 255) / 256 : 4096);
-      hipLaunchKernelGGL(gs_sub_sym_kernel, dim3(grid), dim3(256), 0, st, (const float*)R, gS, D, mdd);
-    } else {
-      DISPATCH_NT(D, hipLaunchKernelGGL((init_bwd_gs_kernel<NT>), dim3(M), dim3(kThreads), 0, st, Z, cur, gS, workspace, D));
-    }
-    if ((rc = launch_status())) return rc;
-  }
-  return uglad_finish_grads(gt_partial, grad_rho_partial, glam_partial, lam_in, params, grad, L, M, stream);
-}
-
-// (Round 3 removed the hipGraph cache of small passes that lived here: once persistent buffers made it hit -- 4 captures, 436 replays in a
-// 220-epoch fit at D = 25 -- the epoch took 1.58 ms with it and 1.51 ms without (profiles/r03_fit_small_graph_probe.txt): a small pass is bound
-// by the latency of its dependent kernels, not by their launches.  The entry points neither allocate nor synchronise, so a caller's own
-// stream capture of a pass still works.)
-int uglad_glad_forward(const float* S, const float* params, float lambda_init, int init_diag, int L, float* Z, int z_slabs,
-                       float* half, float* U, float* beta, float* lam, float* lam_in, float* nf_partial, float* nf_sum,
-                       float* cond_max, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream) {
-  return enqueue_glad_forward(S, params, lambda_init, init_diag, L, Z, z_slabs, half, U, beta, lam, lam_in, nf_partial, nf_sum, cond_max,
-                              workspace, M, D, sqrt_mode, stream);
-}
-
-int uglad_glad_backward(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
-                        const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
-                        float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
-                        float* grad, float* workspace, int M, int D, int sqrt_mode, uglad_stream_t stream) {
-  return enqueue_glad_backward(G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial, glam_partial,
-                               gt_partial, grad, workspace, M, D, sqrt_mode, stream);
-}
-
-int uglad_glad_forward_grouped(const float* S, const float* params, float lambda_init, int init_diag, int L, float* Z,
-                               int z_slabs, float* half, float* U, float* beta, float* lam, float* lam_in, float* nf_partial,
-                               float* nf_sum, float* cond_max, float* workspace, int M, int D, int groups, int sqrt_mode,
-                               uglad_stream_t stream) {
-  if (groups < 1 || M < groups || M % groups != 0) return UGLAD_E_DIM;
-  GroupScope scope(groups);
-  return uglad_glad_forward(S, params, lambda_init, init_diag, L, Z, z_slabs, half, U, beta, lam, lam_in, nf_partial, nf_sum,
-                            cond_max, workspace, M, D, sqrt_mode, stream);
-}
-
-int uglad_glad_backward_grouped(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
-                                const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
-                                float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
-                                float* grad, float* workspace, int M, int D, int groups, int sqrt_mode, uglad_stream_t stream) {
-  if (groups < 1 || M < groups || M % groups != 0) return UGLAD_E_DIM;
-  GroupScope scope(groups);
-  return uglad_glad_backward(G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial,
-                             glam_partial, gt_partial, grad, workspace, M, D, sqrt_mode, stream);
-}
-
-int uglad_glad_backward_wrt_s(const float* G_L, const float* S, const float* params, int init_diag, int L, const float* Z,
-                              const float* half, const float* U, const float* beta, const float* lam, const float* lam_in,
-                              float* gbuf0, float* gbuf1, float* grad_rho_partial, float* glam_partial, float* gt_partial,
-                              float* grad, float* workspace, int M, int D, int groups, int sqrt_mode, float* gS, uglad_stream_t stream) {
-  if (!gS || (D > 128 && !workspace)) return UGLAD_E_NULL;
-  if (groups < 1 || M < groups || M % groups != 0) return UGLAD_E_DIM;
-  CHECK_DIMS(M, D);
-  if (sqrt_mode != UGLAD_SQRT_EXACT && sqrt_mode != UGLAD_SQRT_NS10) return UGLAD_E_MODE;
-  if (init_diag != 0 && init_diag != 1) return UGLAD_E_MODE;
-  GroupScope scope(groups);
-  return enqueue_glad_backward(G_L, S, params, init_diag, L, Z, half, U, beta, lam, lam_in, gbuf0, gbuf1, grad_rho_partial, glam_partial,
-                               gt_partial, grad, workspace, M, D, sqrt_mode, stream, gS);
-}
-
-// ---- the sharded pass as ONE call (collective site i)
-int uglad_glad_forward_sharded(const float* S, const float* params, float lambda_init, int init_diag, int L, float* Z, int z_slabs,
-                               float* half, float* U, float* beta, float* lam, float* lam_in, float* nf_partial, float* nf_sum,
-                               float* cond_max, float* workspace, int M, int D, int m_global, int sqrt_mode,
-                               uglad_allreduce_fn exchange, void* exchange_ctx, uglad_stream_t stream) {
-  if (!exchange) return UGLAD_E_NULL;
-  if (m_global < M || t_groups != 1) return UGLAD_E_DIM;
-  return enqueue_glad_forward(S, params, lambda_init, init_diag, L, Z, z_slabs, half, U, beta, lam, lam_in, nf_partial, nf_sum, cond_max,
-                              workspace, M, D, sqrt_mode, stream, m_global, exchange, exchange_ctx);
-}
-
-// ---- RCCL as the exchange: resolved at run time from the RCCL that is already in the process (PyTorch-ROCm's) or, failing that, the
-// system's -- libuglad_hip.so itself has no link-time dependency on it.
-}  // extern "C"
-#ifndef UGLAD_SIMT_EMUL
-#include <dlfcn.h>
-namespace {
-struct RcclApi {
-  int (*GetUniqueId)(void*) = nullptr;
-  int (*CommInitRank)(void**, int, uglad_rccl_id, int) = nullptr;  // (ncclUniqueId travels by value: 128 bytes)
-  int (*CommDestroy)(void*) = nullptr;
-  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*CommCount)(void*, int*) = nullptr;
-  bool ok = false;
-};
-const RcclApi& rccl_api() {
-  static const RcclApi api = [] {
-    RcclApi a;
-    void* h = nullptr;
-    for (const char* name : {"librccl.so.1", "librccl.so"})
-      if (!h) h = dlopen(name, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);  // the copy PyTorch has loaded, if any
-    for (const char* name : {"librccl.so.1", "librccl.so"})
-      if (!h) h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-    if (!h) return a;
-    a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(dlsym(h, "ncclGetUniqueId"));
-    a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(dlsym(h, "ncclCommInitRank"));
-    a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(dlsym(h, "ncclCommDestroy"));
-    a.AllReduce = reinterpret_cast<decltype(a.AllReduce)>(dlsym(h, "ncclAllReduce"));
-    a.CommCount = reinterpret_cast<decltype(a.CommCount)>(dlsym(h, "ncclCommCount"));
-    a.ok = a.GetUniqueId && a.CommInitRank && a.CommDestroy && a.AllReduce;
-    return a;
-  }();
-  return api;
-}
-constexpr int kNcclFloat32 = 7, kNcclSum = 0;  // rccl.h: ncclDataType_t / ncclRedOp_t
-}  // namespace
-#endif
-extern "C" {
-
-int uglad_rccl_unique_id(uglad_rccl_id* id_out) {
-  if (!id_out) return UGLAD_E_NULL;
-#ifndef UGLAD_SIMT_EMUL
-  if (!rccl_api().ok) return UGLAD_E_RCCL;
-  return rccl_api().GetUniqueId(id_out) == 0 ? 0 : UGLAD_E_RCCL;
-#else
-  return UGLAD_E_RCCL;
-#endif
-}
-
-int uglad_rccl_comm_init(const uglad_rccl_id* id, int nranks, int rank, void** comm_out) {
-  if (!id || !comm_out) return UGLAD_E_NULL;
-  if (nranks < 1 || rank < 0 || rank >= nranks) return UGLAD_E_DIM;
-#ifndef UGLAD_SIMT_EMUL
-  if (!rccl_api().ok) return UGLAD_E_RCCL;
-  return rccl_api().CommInitRank(comm_out, nranks, *id, rank) == 0 ? 0 : UGLAD_E_RCCL;
-#else
-  return UGLAD_E_RCCL;
-#endif
-}
-
-int uglad_rccl_comm_destroy(void* comm) {
-  if (!comm) return UGLAD_E_NULL;
-#ifndef UGLAD_SIMT_EMUL
-  if (!rccl_api().ok) return UGLAD_E_RCCL;
-  return rccl_api().CommDestroy(comm) == 0 ? 0 : UGLAD_E_RCCL;
-#else
-  return UGLAD_E_RCCL;
-#endif
-}
-
-// ncclCommCount: how many ranks the communicator spans -- what a multi-GPU record can show to prove that RCCL saw all of them
-int uglad_rccl_comm_count(void* comm, int* nranks_out) {
-  if (!comm || !nranks_out) return UGLAD_E_NULL;
-#ifndef UGLAD_SIMT_EMUL
-  if (!rccl_api().ok || !rccl_api().CommCount) return UGLAD_E_RCCL;
-  return rccl_api().CommCount(comm, nranks_out) == 0 ? 0 : UGLAD_E_RCCL;
-#else
-  return UGLAD_E_RCCL;
-#endif
-}
-
-// (has the signature of uglad_allreduce_fn: hand its address and the communicator to uglad_glad_forward_sharded)
-int uglad_rccl_allreduce_sum(float* buf, int n, void* comm, uglad_stream_t stream) {
-  if (!buf || !comm) return UGLAD_E_NULL;
-  if (n < 1) return UGLAD_E_DIM;
-#ifndef UGLAD_SIMT_EMUL
-  if (!rccl_api().ok) return UGLAD_E_RCCL;
-  return rccl_api().AllReduce(buf, buf, (size_t)n, kNcclFloat32, kNcclSum, comm, (hipStream_t)stream) == 0 ? 0 : UGLAD_E_RCCL;
-#else
-  return UGLAD_E_RCCL;
-#endif
-}
-
-int uglad_consensus_partial(const float* theta_K, int K, int D, float* absmin, float* signsum, uglad_stream_t stream) {
-  if (!theta_K || !absmin || !signsum) return UGLAD_E_NULL;
-  if (K < 1 || D < 1) return UGLAD_E_DIM;
-  const int DD = D * D;
-  hipLaunchKernelGGL(consensus_partial_kernel, dim3((DD + 255) / 256), dim3(256), 0, (hipStream_t)stream, theta_K, K, DD,
-                     absmin, signsum);
-  return launch_status();
-}
-
-int uglad_consensus_combine(const float* absmin, const float* signsum, int D, float* out, uglad_stream_t stream) {
-  if (!absmin || !signsum || !out) return UGLAD_E_NULL;
-  if (D < 1) return UGLAD_E_DIM;
-  const int DD = D * D;
-  hipLaunchKernelGGL(consensus_combine_kernel, dim3((DD + 255) / 256), dim3(256), 0, (hipStream_t)stream, absmin, signsum,
-                     DD, out);
-  return launch_status();
-}
-
-int uglad_symeig(const float* A, float* U, float* beta, float* workspace, int M, int D, uglad_stream_t stream) {
-  if (!A || !U || !beta || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(M, D);
-  hipStream_t st = (hipStream_t)stream;
-  LAUNCH_TRIDIAG(A, (const float*)nullptr, (const float*)nullptr, U, workspace);
-  float* Tws = workspace + (size_t)M * 3 * padded_dim(D);
-  DISPATCH_NT(D, hipLaunchKernelGGL((symeig_lean_kernel<NT>), dim3(M), dim3(kThreads), 0, st, U, beta, workspace, Tws, D));
-  return launch_status();
-}
-
-int uglad_covariance(const float* X, int K, int N, int D, int normalize, float eval_offset, float* S_out, float* eig_scratch,
-                     float* workspace, uglad_stream_t stream) {
-  if (!X || !S_out) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(K, D);
-  if (N < 1) return UGLAD_E_DIM;
-  if (normalize != 0 && normalize != 1) return UGLAD_E_MODE;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_NT(D, hipLaunchKernelGGL((cov_kernel<NT>), dim3(K), dim3(kThreads), 0, st, X, N, D, normalize, S_out));
-  int rc = launch_status();
-  if (rc || !eig_scratch) return rc;  // eig_scratch == NULL: no eigenvalue repair
-  if (!workspace) return UGLAD_E_NULL;
-  float* beta = eig_scratch + (size_t)K * D * D;
-  if ((rc = uglad_symeig(S_out, eig_scratch, beta, workspace, K, D, stream))) return rc;
-  hipLaunchKernelGGL(cov_repair_kernel, dim3(K), dim3(256), 0, st, S_out, beta, D, eval_offset);
-  return launch_status();
-}
-
-
-#ifdef UGLAD_PHASE_EXIT
-int uglad_diag_set_exit(int at) {  // (development build: see eig_dc.h)
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_exit_at), &at, sizeof(int));
-}
-#endif
-
-#ifdef UGLAD_STAMPS
-int uglad_diag_tstamps(unsigned long long* host_out, int reset) {
-  unsigned long long zero[4] = {0, 0, 0, 0};
-  const hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_tstamps), sizeof(zero));
-  if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tstamps), zero, sizeof(zero));
-  return (int)e;
-}
-
-int uglad_diag_twg(unsigned long long* host_out, int n) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_twg), sizeof(unsigned long long) * 3 * (size_t)n);
-}
-
-int uglad_diag_cwg(unsigned long long* host_out, int n) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_cwg), sizeof(unsigned long long) * 3 * (size_t)n);
-}
-
-int uglad_diag_sec(unsigned long long* host_out) {  // 16 x 8 stamps of the secular solver (eig_lean.h)
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_sec), sizeof(unsigned long long) * 16 * 8);
-}
-
-int uglad_diag_lstamps(unsigned long long* host_out) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_lstamps), sizeof(unsigned long long) * 4 * 96);
-}
-
-int uglad_diag_kstamps(unsigned long long* host_out) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_kstamps), sizeof(unsigned long long) * 32);
-}
-
-int uglad_symeig_stamps(const float* A, float* U, float* beta, float* workspace, int M, int D, unsigned long long* stamps,
-                        uglad_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
-  LAUNCH_TRIDIAG(A, (const float*)nullptr, (const float*)nullptr, U, workspace);
-  DISPATCH_NT(D, hipLaunchKernelGGL((symeig_stamp_kernel<NT>), dim3(M), dim3(kThreads), 0, st, U, beta,
-                                    workspace, D, stamps));
-  return launch_status();
-}
-#endif
-
-int uglad_conditional_mean(const float* precision, const float* mean, const float* observed, const float* values,
-                           float* full_mean, float* cond_cov, float* log_pdf, float* scratch, float* workspace, int K, int D,
-                           int clip01, uglad_stream_t stream) {
-  if (!precision || !mean || !observed || !values || !full_mean || !cond_cov || !scratch || !workspace) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(K, D);
-  hipStream_t st = (hipStream_t)stream;
-  const int M = K;
-  const size_t total = (size_t)K * D * D;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(map_prepare_kernel, dim3(grid), dim3(256), 0, st, precision, observed, scratch, D, total);
-  LAUNCH_TRIDIAG(scratch, (const float*)nullptr, (const float*)nullptr, cond_cov, workspace);
-  DISPATCH_NT(D, hipLaunchKernelGGL((map_solve_kernel<NT>), dim3(K), dim3(kThreads), 0, st, precision, mean, observed, values,
-                                    scratch, full_mean, cond_cov, log_pdf, workspace, D, clip01));
-  return launch_status();
-}
-
-int uglad_partial_correlations(const float* precision, float* rho, int K, int D, uglad_stream_t stream) {
-  if (!precision || !rho) return UGLAD_E_NULL;
-  if (K < 1 || D < 1) return UGLAD_E_DIM;
-  const size_t total = (size_t)K * D * D;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(partial_corr_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, precision, rho, D, total);
-  return launch_status();
-}
-
-int uglad_support_metrics(const float* true_theta, const float* pred_theta, double* out, int K, int D, int beta,
-                          uglad_stream_t stream) {
-  if (!true_theta || !pred_theta || !out) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(K, D);
-  if (D < 2) return UGLAD_E_DIM;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_NT(D, hipLaunchKernelGGL((support_metrics_kernel<NT>), dim3(K), dim3(kThreads), 0, st, true_theta, pred_theta, out, D,
-                                    beta));
-  return launch_status();
-}
-
-int uglad_tridiagonalize(const float* A0, const float* A1, const float* lam, float* R, float* workspace, int M, int D,
-                         uglad_stream_t stream) {
-  if (!A0 || !R || !workspace || (A1 && !lam)) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(M, D);
-  hipStream_t st = (hipStream_t)stream;
-  LAUNCH_TRIDIAG(A0, A1, lam, R, workspace);
-  return launch_status();
-}
-
-int uglad_symeig_jacobi(const float* A, float* U, float* beta, int M, int D, uglad_stream_t stream) {
-  if (!A || !U || !beta) return UGLAD_E_NULL;
-  CHECK_DIMS_EIG(M, D);
-  if (D > 128) return UGLAD_E_DIM;  // LDS-resident only
-  hipStream_t st = (hipStream_t)stream;
-  switch ((D + 31) / 32) {
-    case 1: hipLaunchKernelGGL((symeig_jacobi_kernel<1>), dim3(M), dim3(kThreads), 0, st, A, U, beta, D); break;
-    case 2: hipLaunchKernelGGL((symeig_jacobi_kernel<2>), dim3(M), dim3(kThreads), 0, st, A, U, beta, D); break;
-    case 3: hipLaunchKernelGGL((symeig_jacobi_kernel<3>), dim3(M), dim3(kThreads), 0, st, A, U, beta, D); break;
-    default: hipLaunchKernelGGL((symeig_jacobi_kernel<4>), dim3(M), dim3(kThreads), 0, st, A, U, beta, D); break;
-  }
-  return launch_status();
-}
-
-}  // extern "C"
+// =============================================================================================== the host layer (no device code)
+#include "host_route.h"
+#include "host_launch.h"
+#include "host_api.h"
+#include "host_rccl.h"
+#include "host_extra.h"
 #endif  // !UGLAD_TU_NT

@@ -1,4 +1,4 @@
-// Householder tridiagonalisation of a SMALL symmetric matrix (D <= 64) by ONE wave, the matrix in its registers, no barrier anywhere.
+// Householder tridiagonalisation of a SMALL symmetric matrix (D <= 32: only NT = 1 is built and dispatched, see below) by ONE wave, the matrix in its registers, no barrier anywhere.
 //
 // tridiag.h spreads a matrix over 128 NT threads and pays, per reflector, two workgroup barriers and an LDS gather of partial sums: ~2,500
 // cycles per step whatever the size, 25 us for a 25 x 25 matrix (BASELINE config 1), 62 us at D = 64 (config 2).  Here lane c holds COLUMN c
