@@ -4,8 +4,11 @@ scratch instructions that sit inside loops (a backward branch spans them) -- rea
 uglad_amd/csrc/libuglad_hip.so with the ROCm LLVM tools; nothing is run on a GPU.
 
     python scripts/kernel_meta.py [--so PATH] [--filter SUBSTR] [--loops] > profiles/rNN_kernel_meta.txt
+    python scripts/kernel_meta.py [--so PATH] --diff OTHER.so
 
 --loops disassembles every kernel that has scratch and counts scratch_load / scratch_store instructions inside backward-branch spans.
+--diff compares the two libraries function by function (kernels and the device functions they call): the resource figures of the table and
+the instruction encodings of the disassembly, addresses left out.  Exit status 1 on any difference -- what a refactor has to leave at 0.
 """
 from __future__ import annotations
 
@@ -115,12 +118,64 @@ def scratch_in_loops(co: str, sym: str):
     return len(scr), inside, len(ins)
 
 
+def functions(so: str, td: str):
+    """({symbol: resource figures} of the kernels, {symbol: [(encoding, text)]} of every function) over all code objects of a library."""
+    os.makedirs(td)
+    cos = extract_code_object(so, td)
+    meta, code = {}, {}
+    for co in [cos] if isinstance(cos, str) else cos:
+        for k in notes(co):
+            meta[k["name"]] = {f: v for f, v in k.items() if f != "name"}
+        cur = None
+        for line in subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout.splitlines():
+            m = re.match(r"[0-9a-fA-F]+ <(.+)>:$", line)
+            if m:
+                cur = code.setdefault(m.group(1), [])
+                continue
+            m = re.match(r"\s+(.*?)\s*//\s*[0-9A-Fa-f]+:\s*(.*)$", line)  # text // address: encoding
+            if m and cur is not None:
+                cur.append((m.group(2).strip(), m.group(1)))
+    return meta, code
+
+
+def diff(so_a: str, so_b: str) -> int:
+    with tempfile.TemporaryDirectory() as td:
+        meta_a, code_a = functions(so_a, os.path.join(td, "a"))
+        meta_b, code_b = functions(so_b, os.path.join(td, "b"))
+    bad = 0
+    for sym in sorted(set(code_a) ^ set(code_b)):
+        print(f"only in {so_a if sym in code_a else so_b}: {sym}")
+        bad += 1
+    same = {True: 0, False: 0}  # by "is a kernel"
+    for sym in sorted(set(code_a) & set(code_b)):
+        why = None
+        if meta_a.get(sym) != meta_b.get(sym):
+            ma, mb = meta_a.get(sym) or {}, meta_b.get(sym) or {}
+            why = "resources " + ", ".join(f"{f} {ma.get(f)} != {mb.get(f)}" for f in sorted(set(ma) | set(mb)) if ma.get(f) != mb.get(f))
+        elif [e for e, _ in code_a[sym]] != [e for e, _ in code_b[sym]]:
+            at = next((i for i, (x, y) in enumerate(zip(code_a[sym], code_b[sym])) if x[0] != y[0]), min(len(code_a[sym]), len(code_b[sym])))
+            why = (f"{len(code_a[sym])} / {len(code_b[sym])} instructions, first difference at instruction {at}: "
+                   f"{code_a[sym][at:at + 1]} != {code_b[sym][at:at + 1]}")
+        if why:
+            print(f"DIFFERENT {sym}: {why}")
+            bad += 1
+        else:
+            same[sym in meta_a] += 1
+    print(f"# {so_a} vs {so_b}: {same[True]} of {len(set(meta_a) | set(meta_b))} kernels and {same[False]} of "
+          f"{len((set(code_a) | set(code_b)) - set(meta_a) - set(meta_b))} device functions identical "
+          f"(resource figures and instruction encodings); {bad} differ")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--so", default=os.path.join(ROOT, "uglad_amd", "csrc", "libuglad_hip.so"))
     ap.add_argument("--filter", default="")
     ap.add_argument("--loops", action="store_true")
+    ap.add_argument("--diff", metavar="OTHER.so", help="compare --so with this library instead of printing the table")
     a = ap.parse_args()
+    if a.diff:
+        return diff(a.so, a.diff)
     with tempfile.TemporaryDirectory() as td:
         cos = extract_code_object(a.so, td)
         if isinstance(cos, str):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B (GPU box) of the lambda step carried by the forward cell's second launch (LamStep, glad_kernels.hip: thread 0 of the workgroup when a
+# Same-box A/B (GPU box) of the lambda step carried by the forward cell's second launch (LamStep, cell_fwd.h: thread 0 of the workgroup when a
 # group holds one matrix; groups of several matrices keep the separate launch -- Route::fuse_lambda, host_route.h) against its own norm_lambda launch (UGLAD_NO_FUSED_LAMBDA=1).
 #   bash scripts/lamstep_ab.sh c1     BASELINE config 1, medians of individually synchronised passes, three alternating rounds
 #   bash scripts/lamstep_ab.sh bench  bench.py at config 3 (the headline) and config 2, three alternating rounds; final_loss must agree to the bit

@@ -1,4 +1,5 @@
-// Body of the cell backward kernel, included twice by glad_kernels.hip (inside namespace uglad, per-NT units):
+// Body of the cell backward kernel, included twice by glad_kernels.hip (inside namespace uglad, between cell_fwd.h and theta0.h; every
+// unit holds both templates, the per-NT units instantiate the first and the -DUGLAD_TU_GS units the second):
 //   UGLAD_CELL_BWD_GS 0: cell_bwd_kernel     -- the 42 parameter gradients and dL/dZ_k;
 //   UGLAD_CELL_BWD_GS 1: cell_bwd_gs_kernel  -- the same, and also dL/dS of every step accumulated into gS (M, D, D), which the caller zeroed
 //                        before the pass: gS += G_B / lam_k (b_k = S / lam_k - Z_k) + the rhoNN input gradient of the S feature.  The thread that

@@ -20,6 +20,9 @@ constexpr int P_LW1 = 29, P_LB1 = 35, P_LW2 = 38, P_LB2 = 41;
 constexpr int kNParam = 42, kNRho = 28;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+struct alignas(16) f4 {
+  float x, y, z, w;
+};
 
 // Ordering point between two phases that ONE wave runs on LDS data of its own (no other wave touches it): the DS unit
 // processes the instructions of a wave in issue order, so on the hardware only the compiler has to be kept from moving
@@ -599,6 +602,49 @@ __device__ __forceinline__ void store_tiles(float* __restrict__ Y, const f32x16 
       T::ij(t, I, J);
 #pragma unroll
       for (int e = 0; e < 16; ++e) Y[(I * 32 + acc_row(e, lane)) * LD + J * 32 + (lane & 31)] = acc[n][e];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ phase stamps of the diagnostic builds
+#ifdef UGLAD_STAMPS
+__device__ unsigned long long g_cwg[4096][3];     // diagnostic build: per workgroup of the last lean cell_fwd: start, end, hardware id
+__device__ unsigned long long g_lstamps[4][96];  // diagnostic build: solver phase stamps of workgroups 0..3 of the last lean cell_fwd
+__device__ unsigned long long g_kstamps[32];  // diagnostic build: phase stamps of workgroup 0 of the last cell_fwd / cell_bwd
+#define KSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_kstamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#elif defined(UGLAD_PHASE_EXIT)  // (g_exit_at: eig_dc.h, which every user of KSTAMP includes)
+#define KSTAMP(i) do { if (g_exit_at == 100 + (i)) __builtin_amdgcn_endpgm(); } while (0)
+#else
+#define KSTAMP(i) do {} while (0)
+#endif
+
+// Coalesced copy of the D x D matrix in LDS (row stride LD) to global memory: 16 bytes per lane and store where the rows allow it
+// (D a multiple of 4 and an aligned destination), else 4.  The tail of such a copy is bound by the number of store
+// instructions, not by bytes.
+__device__ __forceinline__ void copy_out_matrix(float* __restrict__ dst, const float* __restrict__ src, int D, int LD) {
+  const int tid = threadIdx.x;
+  if (((D & 3) == 0) && ((reinterpret_cast<size_t>(dst) & 15) == 0)) {
+    // (a half wave reads one row as 32 pieces of 16 bytes: stride 4 over the odd row stride, 8 banks hit four times.  Dealt out as
+    // 4 rows x 8 pieces the reads are conflict-free, but a half wave's store is then four 128-byte segments instead of 512 contiguous
+    // bytes and the forward cell as a whole 1.3 % slower on a same-box A/B: profiles/r03_lean_phase_counters.txt)
+    const int D4 = D >> 2;
+    for (int idx = tid; idx < D * D4; idx += kThreads) {
+      const int i = idx / D4, j = 4 * (idx - i * D4);
+      const float* p = src + i * LD + j;
+      f4 v = {p[0], p[1], p[2], p[3]};
+      *reinterpret_cast<f4*>(dst + (size_t)i * D + j) = v;
+    }
+  } else {
+    const int si = kThreads / D, sj = kThreads - si * D;
+    int i = tid / D, j = tid - i * D;
+    for (int idx = tid; idx < D * D; idx += kThreads) {
+      dst[idx] = src[i * LD + j];
+      j += sj;
+      i += si;
+      if (j >= D) {
+        j -= D;
+        ++i;
+      }
     }
   }
 }

@@ -1,4 +1,5 @@
-// Host layer, part 1 of 5 (glad_kernels.hip includes them in this order; none of them holds device code):
+// Host layer, part 1 of 5 (glad_kernels.hip, the manifest of the library, includes them in this order after the kernel headers and its
+// instantiation lists -- in the host unit and the single-unit build, not in the per-NT units; none of them holds device code):
 //   host_route.h   build limits, the run-time switches, the dispatch on NT, Route (which kernels a call launches), workspace layouts
 //   host_launch.h  the launch sequence of every path
 //   host_api.h     the extern "C" entry points of the pass: validate, build a Route, call host_launch.h

@@ -26,10 +26,6 @@ __device__ unsigned long long g_twg[4096][3];  // per workgroup: start, end (s_m
 #define TSTAMP_ADD(i) do {} while (0)
 #endif
 
-struct alignas(16) f4 {
-  float x, y, z, w;
-};
-
 __device__ __forceinline__ float f4_elem(const f4& a, int q) { return q == 0 ? a.x : (q == 1 ? a.y : (q == 2 ? a.z : a.w)); }
 
 // v[idx] for a wave-uniform idx without dynamic register indexing

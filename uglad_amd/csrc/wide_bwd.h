@@ -19,7 +19,6 @@
 // the region the forward uses for (d, e, tau) and the T factors.
 #pragma once
 #include "glad_device.h"
-#include "tridiag.h"  // f4
 
 namespace uglad {
 
