@@ -4,9 +4,12 @@ scratch instructions that sit inside loops (a backward branch spans them) -- rea
 uglad_amd/csrc/libuglad_hip.so with the ROCm LLVM tools; nothing is run on a GPU.
 
     python scripts/kernel_meta.py [--so PATH] [--filter SUBSTR] [--loops] > profiles/rNN_kernel_meta.txt
+        (--loops disassembles every kernel of the table: about a minute for the whole library, seconds with --filter)
     python scripts/kernel_meta.py [--so PATH] --diff OTHER.so
 
---loops disassembles every kernel that has scratch and counts scratch_load / scratch_store instructions inside backward-branch spans.
+--loops disassembles every kernel and counts scratch_load / scratch_store instructions inside backward-branch spans, the global load
+instructions (gld) and the s_waitcnt with vmcnt <= 1 (vmwait): a kernel that waits about as often as it loads fetches its data one round
+trip at a time (an `inside ? load : 0` that became a branch per entry, a load whose register another load's address was allocated into).
 --diff compares the two libraries function by function (kernels and the device functions they call): the resource figures of the table and
 the instruction encodings of the disassembly, addresses left out.  Exit status 1 on any difference -- what a refactor has to leave at 0.
 """
@@ -93,16 +96,24 @@ def demangle(names):
     return dict(zip(names, out)) if len(out) == len(names) else {n: n for n in names}
 
 
-def scratch_in_loops(co: str, sym: str):
-    """(scratch instructions, of them inside a backward-branch span, instructions) for one kernel symbol."""
+def kernel_instr_stats(co: str, sym: str):
+    """(scratch instructions, of them inside a backward-branch span, instructions, global loads, s_waitcnt with vmcnt <= 1) for one kernel
+    symbol."""
     txt = subprocess.run([f"{LLVM}/llvm-objdump", "-d", f"--disassemble-symbols={sym}", co], capture_output=True, text=True).stdout
     ins = []  # (addr, mnemonic, target or None)
+    loads = waits = 0
     for line in txt.splitlines():
         m = re.match(r"\s+(\S+)\s+(.*?)//\s*([0-9A-Fa-f]+):", line)
         if not m:
             continue
         addr = int(m.group(3), 16)
         mn = m.group(1)
+        if mn.startswith(("global_load", "flat_load", "buffer_load")):
+            loads += 1
+        elif mn == "s_waitcnt":
+            mv = re.search(r"vmcnt\((\d+)\)", m.group(2))
+            if mv and int(mv.group(1)) <= 1:
+                waits += 1
         tgt = None
         if mn.startswith("s_cbranch") or mn == "s_branch":
             mt = re.search(r"<[^>+]+\+0x([0-9a-fA-F]+)>", line)
@@ -110,12 +121,12 @@ def scratch_in_loops(co: str, sym: str):
                 tgt = int(mt.group(1), 16)
         ins.append((addr, mn, tgt))
     if not ins:
-        return 0, 0, 0
+        return 0, 0, 0, 0, 0
     base = ins[0][0]
     spans = [(base + t, a) for a, mn, t in ins if t is not None and base + t <= a]
     scr = [a for a, mn, _ in ins if mn.startswith("scratch_")]
     inside = sum(1 for a in scr if any(lo <= a <= hi for lo, hi in spans))
-    return len(scr), inside, len(ins)
+    return len(scr), inside, len(ins), loads, waits
 
 
 def functions(so: str, td: str):
@@ -193,7 +204,7 @@ def main():
         print(f"# {os.path.relpath(a.so, ROOT)}: {len(rows)} kernels in {len(cos)} gfx950 code object(s)")
         hdr = f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'agpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratchB':>8s} {'ldsB':>7s}"
         if a.loops:
-            hdr += f" {'scr_ins':>7s} {'in_loops':>8s}"
+            hdr += f" {'scr_ins':>7s} {'in_loops':>8s} {'gld':>5s} {'vmwait':>6s}"
         print(hdr)
         for k in rows:
             line = (f"{k['pretty'][:58]:58s} {k.get('max_flat_workgroup_size', '?'):>5s} {k.get('vgpr_count', '?'):>5s} "
@@ -201,11 +212,8 @@ def main():
                     f"{k.get('sgpr_spill_count', '0'):>6s} {k.get('private_segment_fixed_size', '0'):>8s} "
                     f"{k.get('group_segment_fixed_size', '0'):>7s}")
             if a.loops:
-                if int(k.get("private_segment_fixed_size", "0") or 0) > 0:
-                    n, inside, tot = scratch_in_loops(k["co"], k["name"])
-                    line += f" {n:7d} {inside:8d}"
-                else:
-                    line += f" {0:7d} {0:8d}"
+                n, inside, tot, loads, waits = kernel_instr_stats(k["co"], k["name"])
+                line += f" {n:7d} {inside:8d} {loads:5d} {waits:6d}"
             print(line)
 
 

@@ -55,51 +55,105 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
     const float c4 = 4.0f / lam, inv_lam2 = 1.0f / (lam * lam);
 
     KSTAMP(0);
-    // U -> sX, and in the first step G_next -> sY (afterwards G is there already): row-major, coalesced, 8 loads in flight per thread.
+    // U -> sX, and in the first step G_next -> sY (afterwards G is there already): row-major, coalesced.
     // The loads are unconditional (a clamped address, the value selected afterwards): with `in ? load : 0` the compiler put every load
     // behind its own branch and an s_waitcnt vmcnt(0), one round trip after the other (30 k instead of 17 k ticks for this phase).
     // (Explicit loops, not a helper taking the destination as a pointer: through a pointer parameter the LDS stores become flat stores
     // that may alias the loads, and the loop serialises completely -- 137 k ticks.)
-    if (first) {  // 16 loads in flight per thread
-      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
-        float u[8], gv[8];
+    //  * D == DP and 16-byte-aligned matrices (wave-uniform test): the matrix is one contiguous block, fetched as 16-byte pieces with no
+    //    index arithmetic.  At DP = 128 a thread issues all its 8 loads (first step: 16, U and G) and waits once; beyond, 8 per batch.
+    //  * otherwise 4-byte loads, 8 per batch (first step: 16), the position (i, k) and the offset advanced from load to load instead of a
+    //    division and a 64-bit multiply-add per element, the offsets 32-bit (load_at): the 8 requests of a batch are in flight together.
+    constexpr int kV4 = DP * DP / 4, kC4 = DP / 4;
+    constexpr bool kFull4 = kV4 % (8 * kThreads) == 0, kFull1 = (DP * DP) % (8 * kThreads) == 0;  // no partial batch: no test per element
+    const bool vec16 = (D == DP) && (((reinterpret_cast<size_t>(U) | (first ? reinterpret_cast<size_t>(Gnext) : 0)) & 15) == 0);
+    if (vec16) {
+      if (first) {
+        for (int v0 = 0; v0 < kV4; v0 += 8 * kThreads) {
+          f4 u[8], gv[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          const int i = idx / DP, k = idx - i * DP;
-          const bool in = (idx < DP * DP) && i < D && k < D;
-          const int at = in ? i * D + k : 0;
-          const float xu = Um[at], xg = Gm[at];
-          u[q] = in ? xu : 0.f;
-          gv[q] = in ? xg : 0.f;
+          for (int q = 0; q < 8; ++q) {
+            const int idx = v0 + q * kThreads + tid;
+            const unsigned at = (kFull4 || idx < kV4) ? 16u * idx : 0u;
+            u[q] = load_at<f4>(Um, at);
+            gv[q] = load_at<f4>(Gm, at);
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int idx = v0 + q * kThreads + tid;
+            if (kFull4 || idx < kV4) {
+              const int i = idx / kC4, k = 4 * (idx - i * kC4);
+              sX[i * LD + k] = u[q].x, sX[i * LD + k + 1] = u[q].y, sX[i * LD + k + 2] = u[q].z, sX[i * LD + k + 3] = u[q].w;
+              sY[i * LD + k] = gv[q].x, sY[i * LD + k + 1] = gv[q].y, sY[i * LD + k + 2] = gv[q].z, sY[i * LD + k + 3] = gv[q].w;
+            }
+          }
         }
+      } else {
+        for (int v0 = 0; v0 < kV4; v0 += 8 * kThreads) {
+          f4 u[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          if (idx < DP * DP) {
-            const int i = idx / DP, k = idx - i * DP;
-            sX[i * LD + k] = u[q];
-            sY[i * LD + k] = gv[q];
+          for (int q = 0; q < 8; ++q) {
+            const int idx = v0 + q * kThreads + tid;
+            u[q] = load_at<f4>(Um, (kFull4 || idx < kV4) ? 16u * idx : 0u);
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int idx = v0 + q * kThreads + tid;
+            if (kFull4 || idx < kV4) {
+              const int i = idx / kC4, k = 4 * (idx - i * kC4);
+              sX[i * LD + k] = u[q].x, sX[i * LD + k + 1] = u[q].y, sX[i * LD + k + 2] = u[q].z, sX[i * LD + k + 3] = u[q].w;
+            }
           }
         }
       }
     } else {
-      for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
-        float u[8];
+      // element idx = tid + kThreads * (number of the load) of the padded DP x DP matrix sits at (i, k); one load further it is
+      // (i + si, k + sk), carried into the next row where k passes DP
+      constexpr int si = kThreads / DP, sk = kThreads - si * DP;
+      int i = tid / DP, k = tid - i * DP;
+      int off = i * D + k;  // of (i, k) in the D x D matrix
+      const int soff = si * D + sk, wrap = D - DP;
+      if (first) {
+        for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
+          float u[8], gv[8];
+          int dst[8];
+          bool in[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          const int i = idx / DP, k = idx - i * DP;
-          const bool in = (idx < DP * DP) && i < D && k < D;
-          const float xu = Um[in ? i * D + k : 0];
-          u[q] = in ? xu : 0.f;
+          for (int q = 0; q < 8; ++q) {
+            in[q] = (kFull1 || idx0 + q * kThreads + tid < DP * DP) && i < D && k < D;
+            const unsigned at = in[q] ? 4u * off : 0u;
+            u[q] = load_at<float>(Um, at);
+            gv[q] = load_at<float>(Gm, at);
+            dst[q] = i * LD + k;
+            i += si, k += sk, off += soff;
+            if (k >= DP) k -= DP, ++i, off += wrap;
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (else the scheduler pairs every load with its store and waits for each in turn)
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            if (kFull1 || idx0 + q * kThreads + tid < DP * DP) {
+              sX[dst[q]] = in[q] ? u[q] : 0.f;
+              sY[dst[q]] = in[q] ? gv[q] : 0.f;
+            }
+          }
         }
+      } else {
+        for (int idx0 = 0; idx0 < DP * DP; idx0 += 8 * kThreads) {
+          float u[8];
+          int dst[8];
+          bool in[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int idx = idx0 + q * kThreads + tid;
-          if (idx < DP * DP) {
-            const int i = idx / DP, k = idx - i * DP;
-            sX[i * LD + k] = u[q];
+          for (int q = 0; q < 8; ++q) {
+            in[q] = (kFull1 || idx0 + q * kThreads + tid < DP * DP) && i < D && k < D;
+            u[q] = load_at<float>(Um, in[q] ? 4u * off : 0u);
+            dst[q] = i * LD + k;
+            i += si, k += sk, off += soff;
+            if (k >= DP) k -= DP, ++i, off += wrap;
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (else the scheduler pairs every load with its store and waits for each in turn)
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            if (kFull1 || idx0 + q * kThreads + tid < DP * DP) sX[dst[q]] = in[q] ? u[q] : 0.f;
           }
         }
       }
@@ -332,7 +386,9 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
           gb[u] = sY[in ? i * LD + j : 0];  // (unconditional reads, clamped addresses: no branch per entry)
           // S_ij again from memory (L2: phase A read it this step) rather than 33 more registers held across the four products, which
           // spilled dL/dZ's direct part (21 VGPRs, reloaded one round trip at a time right here: 8 k ticks)
-          sij[u] = Sm[in ? i * D + j : 0];
+          // (a 32-bit offset: all of a pass's requests are issued before the first is waited for -- formed as Sm[i * D + j] with a 64-bit
+          // multiply-add, every one of them was followed by an s_waitcnt vmcnt(0), one round trip per entry)
+          sij[u] = load_at<float>(Sm, in ? 4u * ((unsigned)i * (unsigned)D + (unsigned)j) : 0u);
         }
         if (kPre) {
           // branch-free: an entry that does not exist writes to the padding column (never read) and adds zero -- with a branch per entry the

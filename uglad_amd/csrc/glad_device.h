@@ -64,6 +64,22 @@ __device__ __forceinline__ int opaque_v(int v) {
   return v;
 }
 
+// The T that lies `bytes` past `base`.  The offset is an unsigned 32-bit BYTE count: the address is base + zext(offset), with no 64-bit
+// multiply-add behind it.  (`base[i * D + k]` with int indices becomes v_mad_u64_u32 with an undefined high half of the addend; the register
+// allocator puts a load that is still in flight there, and a batch of loads that nothing orders is cut in two by a wait.)
+template <typename T>
+__device__ __forceinline__ T load_at(const float* __restrict__ base, unsigned bytes) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + bytes);
+}
+
+// The same for a float: the value exists, in a register, where this stands -- the computation that leads to it is not sunk to its first use.
+__device__ __forceinline__ float opaque_f(float v) {
+#ifndef UGLAD_SIMT_EMUL
+  asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
+
 // The lane index from the hardware (two instructions, no input register), opaque to the optimiser: where a kernel is held to a register
 // budget, a `lane` that stays live across a long loop body costs a register -- or, spilled, a scratch reload per iteration.
 __device__ __forceinline__ int lane_now() {

@@ -125,26 +125,104 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
   float* tri = tri_base + (size_t)blockIdx.x * 3 * DP;
   const float inv_lam = lam_ptr ? 1.0f / lam_ptr[blockIdx.x / gs] : 1.0f;  // gs matrices share one lambda (one group)
 
-  // ---- load: coalesced along the rows of A (32 lanes x 16 bytes per column)
+  // ---- load: coalesced along the rows of A (32 lanes x 16 bytes per column), LB column slots per batch.  Every load of a batch is
+  // unconditional -- an entry outside the matrix reads the matrix's own first element and is replaced by zero afterwards -- so the
+  // requests of a batch are in flight together and the batch waits once; with `inside ? load : 0` every entry had a branch, a load and an
+  // s_waitcnt vmcnt(0) of its own, 32 round trips per thread one after the other.  Rows 4 r4 .. 4 r4 + 3 of a column are one 16-byte load
+  // where they are contiguous and aligned (D a multiple of 4, aligned bases: the rule of copy_out_matrix), four 4-byte loads otherwise;
+  // the values, and the arithmetic on them, are the same.  (NT = 4: a batch of four slots holds 2 x 16 registers in flight, within the 64.)
   f4 a[NC];
+  {
+    // (the entries are pinned where their batch ends: left alone, the compiler sinks the multiply-add and the select of a slot to the slot's
+    // first use in the step loop and keeps S, Z and the masks of ALL slots until then -- beyond D = 128 twice the registers, and spills)
+    auto pin = [](float v) { return opaque_f(v); };
+    // column slots per batch of 16-byte / of 4-byte loads.  The latter carry a 64-bit address register pair per dword, 16 loads and 16 pairs
+    // at two slots: NT = 3, with all its six slots in registers under the 64-register bound, takes one (two spill a register)
+    constexpr int LB = 4, LS = (NT == 3) ? 1 : 2;
+    const float* __restrict__ Am = A0 + base;
+    const float* __restrict__ Zm = A1 ? A1 + base : nullptr;
+    const bool vec16 = !kDppSum && ((D & 3) == 0) && (((reinterpret_cast<size_t>(A0) | reinterpret_cast<size_t>(A1)) & 15) == 0);
+    if (vec16) {
+      const bool row_in = cg < NCG && 4 * r4 < n;  // (D % 4 == 0: the four rows are inside or outside together)
 #pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    const int c = cg + NCG * i;
-    float t[4];
+      for (int i0 = 0; i0 < NC; i0 += LB) {
+        f4 s[LB], z[LB];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = 4 * r4 + q;
-      float v = 0.f;
-      if (cg < NCG && c < n && r < n) {
-        // (kDppSum: consecutive lanes hold consecutive COLUMNS -- read the mirror entry, 16 lanes = 64 contiguous bytes; the matrix is symmetric)
-        const size_t at = kDppSum ? base + (size_t)r * D + c : base + (size_t)c * D + r;
-        v = A0[at];
-        if (A1) v = fmaf(inv_lam, v, -A1[at]);
+        for (int u = 0; u < LB; ++u) {
+          const int c = cg + NCG * (i0 + u);
+          const unsigned at = (i0 + u < NC && row_in && c < n) ? 4u * (c * D + 4 * r4) : 0u;
+          s[u] = load_at<f4>(Am, at);
+        }
+        if (A1) {
+#pragma unroll
+          for (int u = 0; u < LB; ++u) {
+            const int c = cg + NCG * (i0 + u);
+            const unsigned at = (i0 + u < NC && row_in && c < n) ? 4u * (c * D + 4 * r4) : 0u;
+            z[u] = load_at<f4>(Zm, at);
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (else -Z of the first slot is formed, and all of S waited for, between the requests for Z)
+        }
+#pragma unroll
+        for (int u = 0; u < LB; ++u) {
+          const int i = i0 + u;
+          if (i < NC) {
+            const bool in = row_in && cg + NCG * i < n;
+            f4 v = s[u];
+            if (A1) v = {fmaf(inv_lam, v.x, -z[u].x), fmaf(inv_lam, v.y, -z[u].y), fmaf(inv_lam, v.z, -z[u].z), fmaf(inv_lam, v.w, -z[u].w)};
+            a[i] = {pin(in ? v.x : 0.f), pin(in ? v.y : 0.f), pin(in ? v.z : 0.f), pin(in ? v.w : 0.f)};
+            if (i < NL) s_a[i < NL ? i : 0][tid] = a[i];
+          }
+        }
       }
-      t[q] = v;
+    } else {
+#pragma unroll
+      for (int i0 = 0; i0 < NC; i0 += LS) {
+        float s[LS][4], z[LS][4];
+#pragma unroll
+        for (int u = 0; u < LS; ++u) {
+          const int c = cg + NCG * (i0 + u);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int r = 4 * r4 + q;
+            const bool in = i0 + u < NC && cg < NCG && c < n && r < n;
+            // (kDppSum: consecutive lanes hold consecutive COLUMNS -- read the mirror entry, 16 lanes = 64 contiguous bytes; the matrix is symmetric)
+            const unsigned at = in ? 4u * (kDppSum ? r * D + c : c * D + r) : 0u;
+            s[u][q] = load_at<float>(Am, at);
+          }
+        }
+        if (A1) {
+#pragma unroll
+          for (int u = 0; u < LS; ++u) {
+            const int c = cg + NCG * (i0 + u);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int r = 4 * r4 + q;
+              const bool in = i0 + u < NC && cg < NCG && c < n && r < n;
+              const unsigned at = in ? 4u * (kDppSum ? r * D + c : c * D + r) : 0u;
+              z[u][q] = load_at<float>(Zm, at);
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < LS; ++u) {
+          const int i = i0 + u;
+          if (i < NC) {
+            float t[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const bool in = cg < NCG && cg + NCG * i < n && 4 * r4 + q < n;
+              float v = s[u][q];
+              if (A1) v = fmaf(inv_lam, v, -z[u][q]);
+              t[q] = pin(in ? v : 0.f);
+            }
+            a[i] = {t[0], t[1], t[2], t[3]};
+            if (i < NL) s_a[i < NL ? i : 0][tid] = a[i];
+          }
+        }
+        // (without it the scheduler starts the next batch's loads, a 64-bit address each, before this batch is consumed, and spills)
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
-    a[i] = {t[0], t[1], t[2], t[3]};
-    if (i < NL) s_a[i < NL ? i : 0][tid] = a[i];
   }
   for (int i = tid; i < DP; i += TH) {
     s_vec[i] = 0.f;

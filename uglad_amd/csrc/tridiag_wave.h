@@ -68,16 +68,38 @@ __global__ __launch_bounds__(64) void tridiag_wave_kernel(const float* __restric
   const float inv_lam = lam_ptr ? 1.0f / lam_ptr[blockIdx.x / gs] : 1.0f;
 
   // ---- load: register r = entry (row hf RPL + r, column c); a wave reads whole rows (the matrix is symmetric)
+  // LR rows per batch (at 16 the kernel passes 64 VGPRs, a wave per SIMD fewer), every load unconditional (an entry outside the matrix
+  // reads the matrix's first element and becomes zero afterwards):
+  // the requests of a batch are in flight together and the batch waits once, where `inside ? load : 0` put every entry behind a branch and
+  // an s_waitcnt vmcnt(0) of its own (see tridiag.h)
   float a[RPL];
+  {
+    const float* __restrict__ Am = A0 + base;
+    const float* __restrict__ Zm = A1 ? A1 + base : nullptr;
+    constexpr int LR = 8;
 #pragma unroll
-  for (int r = 0; r < RPL; ++r) {
-    const int row = hf * RPL + r;
-    float v = 0.f;
-    if (row < n && c < n) {
-      v = A0[base + (size_t)row * D + c];
-      if (A1) v = fmaf(inv_lam, v, -A1[base + (size_t)row * D + c]);
+    for (int r0 = 0; r0 < RPL; r0 += LR) {
+      float s[LR], z[LR];
+#pragma unroll
+      for (int u = 0; u < LR; ++u) {
+        const int row = hf * RPL + r0 + u;
+        s[u] = Am[(row < n && c < n) ? row * D + c : 0];
+      }
+      if (A1) {
+#pragma unroll
+        for (int u = 0; u < LR; ++u) {
+          const int row = hf * RPL + r0 + u;
+          z[u] = Zm[(row < n && c < n) ? row * D + c : 0];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < LR; ++u) {
+        const int row = hf * RPL + r0 + u;
+        float v = s[u];
+        if (A1) v = fmaf(inv_lam, v, -z[u]);
+        a[r0 + u] = (row < n && c < n) ? v : 0.f;
+      }
     }
-    a[r] = v;
   }
   // entries of d | e | tau no step writes
   for (int i = lane; i < DP; i += 64) {
