@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import eigen_path_checks
 from oracle import glad_exact as ex
 from oracle import glad_ns as ns
 
@@ -1442,3 +1443,26 @@ def test_cholesky_inverse_logdet_and_the_eigen_fallback(lib, D):
         want = -ld + float(np.sum(S[0].astype(np.float64) * Th[m].astype(np.float64).T))
         assert abs(lp[m] - want) < 2e-6 * max(1.0, abs(want)) + 1e-4, (m, lp[m], want)
     assert max_relF(tinv[:4].cpu().numpy(), np.linalg.inv(Th[:4].astype(np.float64))) < 1e-6
+
+
+@pytest.mark.parametrize("D", [1, 2, 3, 33, 128, 129, (129, "one workgroup")])
+def test_theta0_and_loss_on_the_eigen_path_for_every_matrix(lib, D, monkeypatch):
+    """UGLAD_CHOLESKY=0: init_inverse_kernel and loss_fwd_kernel on the cell's eigensolver (csrc/eig_lean.h) for every matrix, against numpy fp64
+    with the bounds of test_cholesky_inverse_logdet_and_the_eigen_fallback.  D = 1, 2: no reflectors (the solver then ends without a barrier of
+    its own); 3: one reflector; 33: ragged NT = 2; 128: the LDS budget; 129: the first size past LDS.  Three matrices of D = 129 are few enough
+    for the route to take the L D L^T factorisation; the second D = 129 case switches that off, so that the one-workgroup kernels with both
+    big buffers in the workspace are what runs."""
+    monkeypatch.setenv("UGLAD_CHOLESKY", "0")
+    if isinstance(D, tuple):
+        D = D[0]
+        monkeypatch.setenv("UGLAD_WIDE_BWD", "0")
+        monkeypatch.setenv("UGLAD_MATRIX_ITERATION", "0")
+    eigen_path_checks.every_matrix_on_the_eigen_path(lib, "cuda", D)
+
+
+def test_flagged_matrices_in_a_batch_larger_than_the_t_region_of_one_matrix(lib, monkeypatch):
+    """D = 7, M = 520 > NT * 512, matrices 0, 1 and 519 not positive definite: the eigen kernels that recompute them keep their T factors in the
+    region whose head holds the Cholesky flags of the whole batch; placed at T + m * NT * 1024 the factors of matrix 0 would overwrite flags that
+    workgroups scheduled later have not read yet."""
+    monkeypatch.setenv("UGLAD_CHOLESKY", "1")
+    eigen_path_checks.flagged_matrices_in_a_large_batch(lib, "cuda")

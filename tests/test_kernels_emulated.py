@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import eigen_path_checks
 from oracle import glad_exact as ex
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -82,6 +83,26 @@ def test_one_structural_prior_for_the_whole_batch(emul):
     assert torch.equal(out[0][1], out[2][1]) and torch.equal(out[1][1], out[2][1])
     with pytest.raises(ValueError):
         uglad_amd.loss_uGLAD(th, S, struct_theta=torch.zeros(2, 8, 8))
+
+
+@pytest.mark.parametrize("D", [1, 2, 3, 33, 128, (129, "one workgroup")])
+def test_theta0_and_loss_on_the_eigen_path_for_every_matrix(emul, D, monkeypatch):
+    """CPU twin of the GPU test of this name (tests/eigen_path_checks.py) at the sizes this build has, NT = 1, 2, 4, 5: init_inverse_kernel and
+    loss_fwd_kernel on csrc/eig_lean.h for every matrix.  (D = 129 on the one-workgroup route only: the route three such matrices take by
+    default, L D L^T, does not touch these kernels.)"""
+    monkeypatch.setenv("UGLAD_CHOLESKY", "0")
+    M = 3
+    if isinstance(D, tuple):
+        D, M = D[0], 1  # (every work-item is a fiber: one matrix at this size)
+        monkeypatch.setenv("UGLAD_WIDE_BWD", "0")
+        monkeypatch.setenv("UGLAD_MATRIX_ITERATION", "0")
+    eigen_path_checks.every_matrix_on_the_eigen_path(emul, "cpu", D, M=M)
+
+
+def test_flagged_matrices_in_a_batch_larger_than_the_t_region_of_one_matrix(emul, monkeypatch):
+    """CPU twin of the GPU test of this name: D = 7, M = 520 > NT * 512 with matrices 0, 1 and 519 flagged by the Cholesky kernels."""
+    monkeypatch.setenv("UGLAD_CHOLESKY", "1")
+    eigen_path_checks.flagged_matrices_in_a_large_batch(emul, "cpu")
 
 
 SMALL_CELLS = ["cell_d16_b3_L6_diag0_fresh", "cell_d16_b3_L6_diag1_fresh", "cell_d16_b3_L6_diag0_trained",

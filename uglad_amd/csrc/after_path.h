@@ -1,4 +1,4 @@
-// Around the unrolled path: the two symeig exports of the unit tests (and the stamp kernel of the diagnostic build), the covariance
+// Around the unrolled path: the two symeig exports of the unit tests, the covariance
 // front-end of fit(), and what follows a fit -- MAP solve, partial correlations, support-recovery metrics.
 #pragma once
 #include "eig_lean.h"
@@ -22,28 +22,6 @@ __global__ __launch_bounds__(kThreads, NT <= 4 ? 4 : 2) void symeig_lean_kernel(
   copy_out_matrix(U + base, sQ, D, LD);
   if (threadIdx.x < D) beta[(size_t)blockIdx.x * D + threadIdx.x] = ws.d[threadIdx.x];
 }
-
-#ifdef UGLAD_STAMPS
-// diagnostic build only: the solver alone, phase stamps of workgroup m copied to stamps[m*64 ..]
-template <int NT>
-__global__ __launch_bounds__(kThreads) void symeig_stamp_kernel(float* __restrict__ U, float* __restrict__ beta,
-                                                                float* __restrict__ tri, int D,
-                                                                unsigned long long* __restrict__ stamps) {
-  constexpr int DP = NT * 32, LD = DP + 1;
-  UGLAD_BIG_BUFFERS(sA, eig_buf0_floats<DP>(), sV, DP * LD, tri)
-  __shared__ __attribute__((aligned(16))) EigScratch<DP> ws;
-  const int tid = threadIdx.x;
-  const size_t base = (size_t)blockIdx.x * D * D;
-  if (tid < 96) ws.stamp[tid] = 0;
-  __syncthreads();
-  UGLAD_STAMP(ws, 0);
-  symeig_from_tridiagonal<NT>(sA, sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, U + base, D);
-  for (int idx = tid; idx < D * D; idx += kThreads) U[base + idx] = sV[(idx / D) * LD + (idx % D)];
-  if (tid < D) beta[(size_t)blockIdx.x * D + tid] = ws.d[tid];
-  __syncthreads();
-  if (tid < 96) stamps[(size_t)blockIdx.x * 96 + tid] = ws.stamp[tid];
-}
-#endif
 
 // =============================================================================================== covariance front-end
 // What fit() does to a table before the hot path: min-max normalisation of the columns
@@ -164,8 +142,8 @@ __global__ __launch_bounds__(kThreads) void map_solve_kernel(const float* __rest
                                                              float* __restrict__ log_pdf, float* __restrict__ tri, int D,
                                                              int clip01) {
   constexpr int DP = NT * 32, LD = DP + 1;
-  UGLAD_BIG_BUFFERS(sA, eig_buf0_floats<DP>(), sV, DP * LD, tri)
-  __shared__ __attribute__((aligned(16))) EigScratch<DP> ws;
+  UGLAD_BIG_BUFFERS(sV, DP * LD, sA, DP * LD, tri)  // eigenvectors ; scratch of spectral_to_global
+  __shared__ __attribute__((aligned(16))) LeanScratch<DP> ws;
   __shared__ float s_f[DP], s_r[DP], s_t[DP], s_y[DP], s_red[8];
   const int tid = threadIdx.x;
   const size_t base = (size_t)blockIdx.x * D * D;
@@ -183,7 +161,8 @@ __global__ __launch_bounds__(kThreads) void map_solve_kernel(const float* __rest
     }
     s_r[tid] = r;
   }
-  symeig_from_tridiagonal<NT>(sA, sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, cond_cov + base, D);
+  symeig_lean<NT>(sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, cond_cov + base, D, tfac_behind_flags<DP>(tri, gridDim.x, blockIdx.x));
+  __syncthreads();  // (the solver ends with a barrier of its own only if there are reflectors, D > 2)
   float lad = 0.f, bad = 0.f, nu = 0.f;
   if (tid < DP) {
     float f = 0.f;

@@ -1,20 +1,51 @@
-// LDS-lean second stage of the eigensolver for matrices that fit the LDS (DP <= 128): ONE DP x (DP+1) matrix in LDS (the
-// eigenvectors Q) plus ~8 KB of vectors, so that two workgroups share a CU and hide each other's latency-bound phases
-// (secular equation, sorting, the short dependent chains between barriers).  Against eig_dc.h:
+// Batched symmetric eigensolver, one matrix per workgroup (gfx950, 512 threads = 8 waves):
+//
+//   1. Householder tridiagonalisation  A = H T H^T in its own kernel (tridiag.h): the matrix lives in REGISTERS, so that kernel
+//      needs little LDS and four workgroups share a CU, hiding each other's serial reflector chains.  It leaves d, e, tau in the
+//      workspace and the reflectors row by row in a slab the caller lends (the slab of its own output, which nothing writes
+//      before step 3 has finished);
+//   2. divide & conquer on T (Cuppen tearing down to 2x2 leaves solved in closed form, log2 n - 1 merge levels): per merge a
+//      secular equation per eigenvalue (LAPACK-style starting point, rational iteration with bracketing, origin shifted to the
+//      nearest pole so all differences are relatively accurate), Gu-Eisenstat re-derivation of z for orthogonality, and the
+//      eigenvector update Q <- Q W as block-diagonal GEMMs on the f32 MFMA.  Instead of LAPACK's deflation (data-dependent
+//      control flow) equal poles are separated by a few ulps and vanishing z components are floored at 1e-6: a backward error
+//      of O(eps ||T||) that keeps every lane on the same code path.  A merge whose coupling is below 8 eps ||.|| is skipped
+//      (sorted only);
+//   3. back-transformation Q <- H Q in blocks of 16 reflectors (compact WY).
+//
+// Steps 2 and 3 are LDS-lean: ONE DP x (DP+1) matrix (the eigenvectors Q; in LDS up to DP = 128, in the workspace beyond) plus
+// ~8 KB of vectors, so that two workgroups share a CU and hide each other's latency-bound phases (secular equation, sorting, the
+// short dependent chains between barriers):
 //   * the merge matrix W is never materialised: every wave generates the entries of its B operand
 //     W'[k][i] = zhat_k / (d_k - lam_i) from four vectors while it issues the MFMAs that consume them; the column norms come
 //     out of the same loop (two LDS adds per column: bit-reproducible);
-//   * the reflectors stay in global memory (the slab of the output the caller lends, L2-resident) and feed the MFMA A operand
-//     directly; the panel Y = V_b Q lives in the accumulator registers of the wave that needs it (the k order of an MFMA chain
-//     is free, so an accumulator tile is a valid B operand as it stands) -- no Y panel, no reflector copy in LDS;
+//   * the reflectors stay in global memory (the lent slab, L2-resident) and feed the MFMA A operand directly; the panel
+//     Y = V_b Q lives in the accumulator registers of the wave that needs it (the k order of an MFMA chain is free, so an
+//     accumulator tile is a valid B operand as it stands) -- no Y panel, no reflector copy in LDS;
 //   * Gram matrix and triangular factor of a reflector block are formed by one wave in registers (lane broadcasts instead of
 //     LDS reads) and handed to the other waves through the caller's workspace.
 #pragma once
 #include <type_traits>
 
-#include "eig_dc.h"
+#include "glad_device.h"
 
 namespace uglad {
+
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// Components of the coupling vector z below this are floored instead of deflated (see the header of this file).
+#ifndef UGLAD_ZFLOOR
+#define UGLAD_ZFLOOR 1e-6f
+#endif
+constexpr float kZFloor = UGLAD_ZFLOOR;
+
+// Product over the LPR (2 or 4) adjacent lanes that share one root / pole / column of the merge step, in every one of them.
+template <int LPR>
+__device__ __forceinline__ float group_prod(float v) {
+  v *= lane_xor1(v);
+  if (LPR == 4) v *= dpp_move<0x4e>(v);  // quad_perm:[2,3,0,1]
+  return v;
+}
 
 // Reflectors are applied in blocks of kRB = 16 (compact WY).  Packed upper triangle of a 16 x 16 Gram matrix: row j keeps
 // columns gtri_start(j) .. 15 (the start rounded down to a multiple of 4 so that a row is read in 16-byte pieces), rows back
@@ -51,11 +82,13 @@ struct LeanScratch {
 };
 
 // ------------------------------------------------------------------------------------------------ secular equation
-// secular_root (eig_dc.h) with the lane's poles held in REGISTERS for the whole solve, relative to the origin pole, and a
-// leaner evaluation: the terms rz_j / (d_j - x) left of the root are the negative ones, so the sums the rational step needs
-// come out of one pass without a per-pole left/right test:  w = 1 + sum t_j,  sum |t_j| (the error bound),
-// dpsi = sum min(t_j, 0) / (d_j - x),  dphi = sum t_j / (d_j - x) - dpsi.  LPR lanes share a root (LPR = 1, 2, 4), NP poles
-// per lane: merges of up to LPR * NP poles.
+// Secular equation 1 + sum_j rz[j] / (ds[j] - x) = 0 (rz = rho z^2, strictly increasing poles ds[0..nb)), root i.  LPR adjacent
+// lanes (LPR = 1, 2, 4, 8; sub = the lane's index among them) share the root: each holds every LPR-th pole, NP of them -- merges of
+// up to LPR * NP poles -- in REGISTERS for the whole solve, relative to the origin pole, and the group combines its sums with
+// cross-lane moves, so all its lanes carry bitwise identical iterates and leave the loop together.  The terms rz_j / (d_j - x)
+// left of the root are the negative ones, so the sums the rational step needs come out of one pass without a per-pole
+// left/right test:  w = 1 + sum t_j,  sum |t_j| (the error bound), and the derivative sums.  Returns the origin pole K and mu
+// with x = ds[K] + mu; the function's value is the number of evaluations of the secular function.
 #ifndef UGLAD_SECULAR_MAXIT
 #define UGLAD_SECULAR_MAXIT 48
 #endif
@@ -96,7 +129,11 @@ __device__ __forceinline__ int secular_root_reg(const float* __restrict__ ds, co
     }
   }
   SEC_STAMP(1);
-  // starting point as in secular_root: evaluate at a test point, keep the two nearest poles exact, freeze the rest
+  // Starting point (as in LAPACK's slaed4): evaluate at a test point -- the midpoint of the two neighbouring poles; for the last
+  // root the root of the two-pole equation 1 + p/(d1 - x) + q/(0 - x) = 0 (all other poles ignored) instead of LAPACK's rho / 2:
+  // it lies close to the root, so freezing the far poles there costs one iteration less on the root that otherwise keeps its
+  // whole wave waiting -- then keep the two nearest poles exact and freeze the rest there:
+  // rest (d1-x)(d2-x) + p (d2-x) + q (d1-x) = 0.
   const bool last = i == nb - 1;
   const int ia = last ? nb - 2 : i;
   const float hi_last = rho * 1.00001f + 1e-30f;
@@ -442,8 +479,9 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
 }
 
 // ------------------------------------------------------------------------------------------------ divide & conquer
-// As dc_tridiagonal (eig_dc.h) up to the roots and the Gu-Eisenstat vector; the eigenvector update Q <- Q W' diag(1/||.||) then
-// generates W' on the fly.
+// Eigen-decomposition of the tridiagonal (ws.d, ws.e) of order n: Q (DP x DP, stride LD = DP+1) receives the eigenvectors, ws.d
+// the eigenvalues in ascending order.  Per level: merged order and z, coupling test, secular roots, the Gu-Eisenstat vector, then
+// the eigenvector update Q <- Q W' diag(1/||.||) with W' generated on the fly.
 // With `last` != nullptr (few large matrices, wide_bwd.h) the LAST merge is only prepared -- merged order, z, coupling test, poles
 // pushed apart -- and handed over in global memory for launches with many workgroups per matrix to carry out:
 //   last[0 .. DP) ds (poles, sorted), [DP .. 2DP) zs, [2DP .. 3DP) rho z^2, [3DP .. 4DP) perm (int), [4DP] rho, [4DP + 1] skip (int).
@@ -459,7 +497,9 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
     Q[i * LD + j] = (i == j) ? 1.f : 0.f;
   }
   __syncthreads();
-  if (2 * tid < n) {  // 2 x 2 leaves in closed form (see dc_tridiagonal)
+  // Leaves are 2 x 2 (the last one 1 x 1 when n is odd), solved in closed form by a Jacobi rotation; the boundaries BETWEEN
+  // leaves are torn: the rows on either side of boundary (2i+1 | 2i+2) give up |e_{2i+1}|.
+  if (2 * tid < n) {
     const int i0 = 2 * tid, i1 = i0 + 1;
     float a = ws.d[i0];
     if (i0 > 0) a -= fabsf(ws.e[i0 - 1]);
@@ -641,7 +681,7 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
         roots(integral_constant<int, LR>(), integral_constant<int, 128 / LR>());  // (64 poles per lane at LR = 2: 256-register kernels only)
       } else {
         // bs = 256 (D > 128): 256 poles are too many for the registers of two or four lanes -- EIGHT lanes per root, 32 poles each,
-        // 64 roots per pass (the LDS-resident solver of eig_dc.h with two lanes per root took 180 k cycles here)
+        // 64 roots per pass (two lanes per root with the poles read from LDS took 180 k cycles here)
         for (int pass = 0; 64 * pass < n; ++pass) {
           const int pr_ = 64 * pass + tid / 8, sb = tid % 8;
           if (pr_ < n) {

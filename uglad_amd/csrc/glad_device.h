@@ -623,15 +623,23 @@ __device__ __forceinline__ void store_tiles(float* __restrict__ Y, const f32x16 
 }
 
 // ------------------------------------------------------------------------------------------ phase stamps of the diagnostic builds
+// -DUGLAD_STAMPS (scripts/stamp_lean.py, stamp_cell.py): shader-clock stamps at phase boundaries -- UGLAD_STAMP(ws, i) inside the
+// eigensolver (into the stamp array of its scratch), KSTAMP(i) in the cell kernels (workgroup 0).
+// -DUGLAD_PHASE_EXIT (scripts/phase_exit_probe.py): every wave ENDS at the boundary g_exit_at names (KSTAMP i: 100 + i), so that
+// hardware counters of launches cut at successive boundaries give per-phase differences (the outputs of such a launch are garbage).
 #ifdef UGLAD_STAMPS
 __device__ unsigned long long g_cwg[4096][3];     // diagnostic build: per workgroup of the last lean cell_fwd: start, end, hardware id
 __device__ unsigned long long g_lstamps[4][96];  // diagnostic build: solver phase stamps of workgroups 0..3 of the last lean cell_fwd
 __device__ unsigned long long g_kstamps[32];  // diagnostic build: phase stamps of workgroup 0 of the last cell_fwd / cell_bwd
 #define KSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_kstamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#elif defined(UGLAD_PHASE_EXIT)  // (g_exit_at: eig_dc.h, which every user of KSTAMP includes)
+#define UGLAD_STAMP(ws, i) do { if (threadIdx.x == 0 && (i) < 64) (ws).stamp[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#elif defined(UGLAD_PHASE_EXIT)
+__device__ int g_exit_at;
 #define KSTAMP(i) do { if (g_exit_at == 100 + (i)) __builtin_amdgcn_endpgm(); } while (0)
+#define UGLAD_STAMP(ws, i) do { if (g_exit_at == (i)) __builtin_amdgcn_endpgm(); } while (0)
 #else
 #define KSTAMP(i) do {} while (0)
+#define UGLAD_STAMP(ws, i) do {} while (0)
 #endif
 
 // Coalesced copy of the D x D matrix in LDS (row stride LD) to global memory: 16 bytes per lane and store where the rows allow it
@@ -663,6 +671,37 @@ __device__ __forceinline__ void copy_out_matrix(float* __restrict__ dst, const f
       }
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------ workspace of the spectral path
+// M (d, e, tau) records | M x kTfacFloats: the triangular factors of the eigensolver's back-transformation (eig_lean.h) |
+// beyond DP = 128, M x two big buffers.  (The host's view of the same layout: EigLayout, host_route.h.)
+template <int DP>
+constexpr int kTfacFloats = (DP / 32) * 1024;
+template <int DP>
+constexpr int kWsPerMatrix = 3 * DP + kTfacFloats<DP>;  // floats per matrix ahead of the big buffers
+template <int DP>
+constexpr int big_floats() {  // both big buffers of a matrix, DP x (DP+1) each, 16-byte granularity
+  return 2 * ((DP * (DP + 1) + 3) & ~3);
+}
+// The two big per-matrix buffers of a kernel: LDS while they fit (DP <= 128); beyond that, slabs of the caller's workspace GWS,
+// which stay L2-resident -- the same code then runs on global pointers, slower but with no size limit from the 160 KB of LDS.
+// NA floats for the first buffer, NB for the second.
+#define UGLAD_BIG_BUFFERS(A, NA, B, NB, GWS)                                                                     \
+  constexpr bool kGM = DP > 128;                                                                                 \
+  __shared__ __attribute__((aligned(16))) float A##_lds[kGM ? 4 : (NA)];                                         \
+  __shared__ __attribute__((aligned(16))) float B##_lds[kGM ? 4 : (NB)];                                         \
+  float* A = kGM ? (GWS) + (size_t)gridDim.x * kWsPerMatrix<DP> + (size_t)blockIdx.x * big_floats<DP>() : A##_lds; \
+  float* B = kGM ? A + big_floats<DP>() / 2 : B##_lds;
+
+// T factors of matrix m for the kernels that run BEHIND the Cholesky kernels (Theta_0, the loss) or share their code (MAP): the
+// first M ints of the T region are the Cholesky flags, which workgroups scheduled later still have to read, so these kernels pack
+// their factors -- half of kTfacFloats per matrix is what one workgroup per matrix uses -- behind the flags, from a 16-byte
+// boundary (the factors are read as f4).  (M + 3) + M kTfacFloats / 2 <= M kTfacFloats for every M >= 1: always inside the region.
+template <int DP>
+__device__ __forceinline__ float* tfac_behind_flags(float* ws, int M, int m) {
+  static_assert(kTfacFloats<DP> / 2 >= 4, "flags and packed T factors outgrow the T region: M + 3 <= M kTfacFloats / 2 needs kTfacFloats / 2 >= 4");
+  return ws + (size_t)M * 3 * DP + ((M + 3) & ~3) + (size_t)m * (kTfacFloats<DP> / 2);
 }
 
 }  // namespace uglad

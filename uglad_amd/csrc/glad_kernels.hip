@@ -7,7 +7,7 @@
 
 #include "../../include/uglad_hip.h"
 #include "glad_device.h"
-#include "eig_dc.h"
+#include "tridiag.h"
 #include "eig_lean.h"
 #include "tridiag_wave.h"
 #include "chol.h"
@@ -67,11 +67,6 @@ namespace uglad {
 // D <= 32: one wave per matrix, the matrix in its registers (tridiag_wave.h)
 #define UGLAD_KERNELS_NT_EQ1(X, NT) X(tridiag_wave_kernel<NT>)
 #define UGLAD_KERNELS_NT_GE5(X, NT) X(tridiag_kernel<NT, 1024>) X(cell_fwd_back_kernel<NT>)
-#ifdef UGLAD_STAMPS
-#define UGLAD_KERNELS_STAMPS(X, NT) X(symeig_stamp_kernel<NT>)
-#else
-#define UGLAD_KERNELS_STAMPS(X, NT)
-#endif
 #if defined(UGLAD_TU_NT) && defined(UGLAD_TU_ONLY)
 // development (scripts/spill_check.sh): -DUGLAD_TU_ONLY='cell_fwd_lean_kernel<4>' emits that kernel alone, to read its register
 // allocation in seconds (UGLAD_TU_ONLY2, UGLAD_TU_ONLY3: further kernels of the same family)
@@ -86,7 +81,6 @@ UGLAD_EMIT(UGLAD_TU_ONLY3)
 UGLAD_KERNELS_GS(UGLAD_EMIT, UGLAD_TU_NT)
 #elif defined(UGLAD_TU_NT)
 UGLAD_KERNELS_EVERY_NT(UGLAD_EMIT, UGLAD_TU_NT)
-UGLAD_KERNELS_STAMPS(UGLAD_EMIT, UGLAD_TU_NT)
 #if UGLAD_TU_NT <= 4
 UGLAD_KERNELS_NT_LE4(UGLAD_EMIT, UGLAD_TU_NT)
 #if UGLAD_TU_NT <= 3
@@ -99,7 +93,7 @@ UGLAD_KERNELS_NT_EQ1(UGLAD_EMIT, UGLAD_TU_NT)
 UGLAD_KERNELS_NT_GE5(UGLAD_EMIT, UGLAD_TU_NT)
 #endif
 #elif defined(UGLAD_TU_HOST)
-#define UGLAD_DECLARE_NT(NT) UGLAD_KERNELS_EVERY_NT(UGLAD_DECLARE, NT) UGLAD_KERNELS_STAMPS(UGLAD_DECLARE, NT) UGLAD_KERNELS_GS(UGLAD_DECLARE, NT)
+#define UGLAD_DECLARE_NT(NT) UGLAD_KERNELS_EVERY_NT(UGLAD_DECLARE, NT) UGLAD_KERNELS_GS(UGLAD_DECLARE, NT)
 UGLAD_DECLARE_NT(1) UGLAD_DECLARE_NT(2) UGLAD_DECLARE_NT(3) UGLAD_DECLARE_NT(4)
 UGLAD_KERNELS_NT_LE4(UGLAD_DECLARE, 1) UGLAD_KERNELS_NT_LE4(UGLAD_DECLARE, 2) UGLAD_KERNELS_NT_LE4(UGLAD_DECLARE, 3) UGLAD_KERNELS_NT_LE4(UGLAD_DECLARE, 4)
 UGLAD_KERNELS_NT_LE3(UGLAD_DECLARE, 1) UGLAD_KERNELS_NT_LE3(UGLAD_DECLARE, 2) UGLAD_KERNELS_NT_LE3(UGLAD_DECLARE, 3)

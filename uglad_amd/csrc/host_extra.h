@@ -56,7 +56,7 @@ int uglad_covariance(const float* X, int K, int N, int D, int normalize, float e
 
 
 #ifdef UGLAD_PHASE_EXIT
-int uglad_diag_set_exit(int at) {  // (development build: see eig_dc.h)
+int uglad_diag_set_exit(int at) {  // (development build: see glad_device.h)
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_exit_at), &at, sizeof(int));
 }
 #endif
@@ -87,17 +87,6 @@ int uglad_diag_lstamps(unsigned long long* host_out) {
 
 int uglad_diag_kstamps(unsigned long long* host_out) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_kstamps), sizeof(unsigned long long) * 32);
-}
-
-int uglad_symeig_stamps(const float* A, float* U, float* beta, float* workspace, int M, int D, unsigned long long* stamps,
-                        uglad_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
-  launch_tridiag(util_route(M, D), st, A, nullptr, nullptr, U, workspace);
-  for_nt(D, [&](auto nt) {
-    hipLaunchKernelGGL((symeig_stamp_kernel<decltype(nt)::value>), dim3(M), dim3(kThreads), 0, st, U, beta,
-                                    workspace, D, stamps);
-  });
-  return launch_status();
 }
 #endif
 

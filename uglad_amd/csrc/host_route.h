@@ -176,15 +176,15 @@ static int check_dims(const Route& r, bool eig_only = false) {
 static bool valid_sqrt(int sqrt_mode) { return sqrt_mode == UGLAD_SQRT_EXACT || sqrt_mode == UGLAD_SQRT_NS10; }
 
 // ---- workspace of the spectral path: M (d, e, tau) records | M x DP / 32 triangular factors of the back-transformation (32 x 32 each; their
-// head doubles as the Cholesky kernels' per-matrix flags, idle then) | beyond D = 128, M x two big buffers.  The kernels' own description of it:
-// kWsPerMatrix<DP>, big_floats<DP>() (eig_dc.h).
+// head doubles as the Cholesky kernels' per-matrix flags; the eigen kernels that run behind them pack their factors past the flags,
+// tfac_behind_flags) | beyond D = 128, M x two big buffers.  The kernels' own description of it: kWsPerMatrix<DP>, big_floats<DP>() (glad_device.h).
 constexpr size_t eig_hdr_floats(int DP) { return 3 * (size_t)DP + (size_t)(DP / 32) * 1024; }
 constexpr size_t eig_slab_floats(int DP) { return 2 * (((size_t)DP * (DP + 1) + 3) & ~(size_t)3); }
 template <int... NT>
 constexpr bool eig_layout_matches_the_kernels(std::integer_sequence<int, NT...>) {
   return ((eig_hdr_floats(32 * (NT + 1)) == (size_t)kWsPerMatrix<32 * (NT + 1)> && eig_slab_floats(32 * (NT + 1)) == (size_t)big_floats<32 * (NT + 1)>()) && ...);
 }
-static_assert(eig_layout_matches_the_kernels(std::make_integer_sequence<int, 8>{}), "EigLayout and eig_dc.h describe different workspaces");
+static_assert(eig_layout_matches_the_kernels(std::make_integer_sequence<int, 8>{}), "EigLayout and glad_device.h describe different workspaces");
 struct EigLayout {
   int DP, LD;                  // padded size; row stride of the big buffers
   size_t rec, tfac, hdr, slab;  // floats per matrix: the record, the T factors, both (the wide backward's partial sums reuse them), the big buffers

@@ -20,8 +20,8 @@ __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(const float* __restr
                                                             float* __restrict__ theta_inv,
                                                             float* __restrict__ tri, int D, const int* __restrict__ only_flagged) {
   constexpr int DP = NT * 32, LD = DP + 1;
-  UGLAD_BIG_BUFFERS(sA, eig_buf0_floats<DP>(), sV, DP * LD, tri)
-  __shared__ __attribute__((aligned(16))) EigScratch<DP> ws;
+  UGLAD_BIG_BUFFERS(sV, DP * LD, sA, DP * LD, tri)  // eigenvectors ; scratch of spectral_to_global
+  __shared__ __attribute__((aligned(16))) LeanScratch<DP> ws;
   __shared__ float s_f[DP], s_red[8];
   if (only_flagged && only_flagged[blockIdx.x] == 0) return;  // (the Cholesky kernel has done this matrix)
   const int tid = threadIdx.x;
@@ -38,7 +38,8 @@ __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(const float* __restr
     }
   }
   tr = block_sum(tr, s_red);
-  symeig_from_tridiagonal<NT>(sA, sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, theta_inv + base, D);
+  symeig_lean<NT>(sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, theta_inv + base, D, tfac_behind_flags<DP>(tri, gridDim.x, blockIdx.x));
+  __syncthreads();  // (the solver ends with a barrier of its own only if there are reflectors, D > 2)
   float lad = 0.f, neg = 0.f, zero = 0.f;
   if (tid < DP) {
     float f = 0.f;

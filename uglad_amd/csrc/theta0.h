@@ -2,7 +2,7 @@
 // MAP solve (spectral_to_global), and the backward kernels for t and for S.
 #pragma once
 #include "chol.h"
-#include "eig_dc.h"
+#include "eig_lean.h"
 
 namespace uglad {
 
@@ -127,7 +127,8 @@ __device__ __forceinline__ void spectral_to_global(float* __restrict__ sA, float
   newton_inverse_to_global<NT>(sA, sV, out, D, Asrc, shift);
 }
 
-// Theta_0 = (S + t I)^-1 through the eigendecomposition of S (the same in-LDS solver as the cell): V diag(1/(s_i + t)) V^T.
+// Theta_0 = (S + t I)^-1 through the eigendecomposition of S (the cell's solver, eig_lean.h): V diag(1/(s_i + t)) V^T.  The
+// eigenvectors land in the first big buffer (sV), the second (sA) is the scratch of spectral_to_global.
 template <int NT>
 __global__ __launch_bounds__(kThreads) void init_inverse_kernel(const float* __restrict__ S,
                                                                 const float* __restrict__ params,
@@ -135,14 +136,15 @@ __global__ __launch_bounds__(kThreads) void init_inverse_kernel(const float* __r
                                                                 float* __restrict__ tri, int D, int gs,
                                                                 const int* __restrict__ only_flagged) {
   constexpr int DP = NT * 32, LD = DP + 1;
-  UGLAD_BIG_BUFFERS(sA, eig_buf0_floats<DP>(), sV, DP * LD, tri)
-  __shared__ __attribute__((aligned(16))) EigScratch<DP> ws;
+  UGLAD_BIG_BUFFERS(sV, DP * LD, sA, DP * LD, tri)
+  __shared__ __attribute__((aligned(16))) LeanScratch<DP> ws;
   __shared__ float s_f[DP];
   if (only_flagged && only_flagged[blockIdx.x] == 0) return;  // (the Cholesky kernel has done this matrix)
   const int tid = threadIdx.x;
   const size_t base = (size_t)blockIdx.x * D * D;
   const float t = params[(size_t)(blockIdx.x / gs) * kNParam + P_T];
-  symeig_from_tridiagonal<NT>(sA, sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, theta0 + base, D);
+  symeig_lean<NT>(sV, D, ws, tri + (size_t)blockIdx.x * 3 * DP, theta0 + base, D, tfac_behind_flags<DP>(tri, gridDim.x, blockIdx.x));
+  __syncthreads();  // (the solver ends with a barrier of its own only if there are reflectors, D > 2)
   if (tid < DP) s_f[tid] = (tid < D) ? 1.0f / (ws.d[tid] + t) : 0.f;
   __syncthreads();
   spectral_to_global<NT>(sA, sV, s_f, theta0 + base, D, S + base, t);
