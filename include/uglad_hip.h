@@ -7,7 +7,8 @@
  * ctypes stub a uGLAD maintainer would add to call these from uglad/glad/glad.py and uglad/main.py.
  *
  * Conventions
- *  - every pointer is a DEVICE pointer to a caller-owned, contiguous, row-major fp32 buffer; sizes are explicit;
+ *  - every pointer is a DEVICE pointer to a caller-owned, contiguous, row-major fp32 buffer; sizes are explicit (the one exception:
+ *    uglad_covariance_wide reads its tables, and returns its eigenvalues, in fp64);
  *  - `stream` is the hipStream_t the work is enqueued on (pass torch's current stream); nothing synchronises;
  *  - no allocation or free of device memory; the library never keeps a device pointer after returning; entry points that
  *    run the eigensolver take a caller-owned `workspace` of uglad_workspace_floats(M, D) floats;
@@ -81,7 +82,8 @@ int uglad_set_wide_mode(int mode);
  * Gershgorin UPPER BOUND of the condition number; Theta_0 and the loss's logdet / inverse use an L D L^T factorisation without
  * pivoting (torch.logdet's rules from the signs of D: finite for an even number of negative eigenvalues, NaN for an odd one; a zero
  * pivot gives NaN where a singular matrix gives -inf in torch).  The entry points of the path (init_theta, cell_fwd / cell_bwd, loss_*, glad_forward* / glad_backward*) take every
- * D <= uglad_max_dim(); uglad_symeig, uglad_cell_fwd_stage2, uglad_tridiagonalize, uglad_covariance, uglad_conditional_mean and
+ * D <= uglad_max_dim(), and so does the covariance front-end through uglad_covariance_wide; uglad_symeig, uglad_cell_fwd_stage2,
+ * uglad_tridiagonalize, uglad_covariance (the fp32 front-end, whose repair runs the eigensolver), uglad_conditional_mean and
  * uglad_support_metrics stay at uglad_max_eig_dim().  A call on this path takes at most 21845 matrices (UGLAD_E_DIM beyond: matrix x
  * product, up to three products, share one grid dimension).
  * The same path is taken automatically (mode -1, the default) for FEW matrices of 128 < D <= 256 under UGLAD_SQRT_NS10, where one
@@ -280,6 +282,21 @@ int uglad_symeig(const float* A, float* U, float* beta, float* workspace, int M,
  * S += (eval_offset - min eig) I.  A constant column under normalize = 1 gives NaN, as in the reference. */
 int uglad_covariance(const float* X, int K, int N, int D, int normalize, float eval_offset, float* S_out, float* eig_scratch,
                      float* workspace, uglad_stream_t stream);
+
+/* The covariance front-end for every D <= uglad_max_dim() -- what the cell covers -- in fp64 and without an eigensolver (csrc/cov_wide.h).
+ * X is a DEVICE pointer to (K, N, D) row-major tables in FP64 (the exception to this header's fp32 convention: the reference's tables
+ * are fp64, and with every operation here in fp64 the only rounding left is the store of S_out).  S_out (K, D, D) fp32 receives the
+ * covariance of the (normalize = 1: min-max normalised) columns, exactly symmetric; a constant column under normalize = 1 gives NaN,
+ * as in the reference.  min_eig_out NULL: no repair.  Otherwise (K doubles) the reference's repair follows: a table whose smallest
+ * eigenvalue is <= 1e-6 gets S += (eval_offset - min eig) I and min_eig_out[k] = that eigenvalue, found to ~1e-13 by bisection on
+ * "S - sigma I has a Cholesky factorisation" (decided in fp64: error <= D (D + 1) 2^-53 tr S); a table that needs no repair gets
+ * min_eig_out[k] = +infinity (its smallest eigenvalue is only known to exceed 1e-6).  Many workgroups per table, 2 + 1 + 25 (2 ceil(D / 64)
+ * + 1) + 1 launches, no host readback.  workspace: uglad_covariance_wide_workspace_floats(K, D) floats, 8-byte aligned (UGLAD_E_NULL
+ * otherwise), always required: per table two fp64 slabs of order D rounded up to 64, the column statistics and the bisection's state.
+ * K <= 65535.  Errors as uglad_covariance; the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+int uglad_covariance_wide_workspace_floats(int K, int D);
+int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, double eval_offset, float* S_out, double* min_eig_out,
+                          float* workspace, uglad_stream_t stream);
 
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
  * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k; workspace receives d, e, tau

@@ -1,0 +1,299 @@
+"""The covariance front-end for every D the cell covers (uglad_covariance_wide, csrc/cov_wide.h): fp64 throughout, the reference's
+repair decided by a Cholesky bisection instead of an eigensolver.  CPU: the unmodified kernel sources on the SIMT emulator (small D:
+the entry point takes every 1 <= D <= max_dim) against the oracle restatement of the reference.  GPU: the widecov_* goldens made by the
+real reference (tests/golden/make_widecov_goldens.py), main's routing, fit() and a graph capture.
+
+Tolerances, both derived:
+  S_out is the fp64 result rounded once per entry, so its relative Frobenius distance from the fp64 reference is <= 2^-24 ~ 6e-8:
+  asserted < 1e-7.
+  |min eig - eigvalsh(S_raw).min()| <= D (D + 1) 2^-53 tr(S) (the backward error of the Cholesky test, Higham Thm 10.3) + 1.2e-13 (the
+  bisection's last interval for tr <= 1e3); S_raw from oracle.covariance.empirical_cov, which test_oracle_matches_reference holds to
+  1e-14 of the reference."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import covariance as ocov
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+TOL = 1e-7  # relative Frobenius: one fp32 rounding per entry
+
+
+def relerr(a, b):
+    return float(np.linalg.norm(np.asarray(a, np.float64) - b) / np.linalg.norm(b))
+
+
+def min_eig_bound(S_raw):
+    D = S_raw.shape[-1]
+    return D * (D + 1) * 2.0 ** -53 * float(np.trace(S_raw)) + 1.2e-13
+
+
+def tables(K, N, D, seed, rank=None):
+    """Tables made the way tests/golden/make_cov_goldens.py makes them (columns on very different scales)."""
+    rng = np.random.default_rng(seed)
+    Xs = []
+    for _ in range(K):
+        A = rng.standard_normal((D, D)) / np.sqrt(D) + np.eye(D)
+        X = rng.standard_normal((N, D)) @ A
+        if rank is not None:
+            X[:, rank:] = X[:, :rank] @ rng.standard_normal((rank, D - rank))
+        Xs.append(X * rng.uniform(0.5, 20.0, size=D) + rng.uniform(-5, 5, size=D))
+    return np.stack(Xs)
+
+
+def run_wide(lib, X64, device, **kw):
+    out = lib.covariance_wide(torch.from_numpy(np.ascontiguousarray(X64, dtype=np.float64)).to(device), **kw)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    return [o.cpu().numpy() for o in out] if isinstance(out, tuple) else out.cpu().numpy()
+
+
+def check_against_oracle(lib, X, device, offset=0.1, expect_repaired=None):
+    """normalize = 1 on the raw tables, against the oracle's normalisation + covariance + repair; returns (S, min eig, repaired)."""
+    Xn = ocov.normalize_min_max(X)
+    S_raw = ocov.empirical_cov(Xn)
+    ref = ocov.get_covariance(Xn, offset=offset)
+    S, mn, rep = run_wide(lib, X, device, normalize=True, eval_offset=offset, repair=True, return_min_eig=True)
+    assert S.dtype == np.float32 and mn.dtype == np.float64 and np.isfinite(S).all()
+    assert np.abs(S - np.swapaxes(S, 1, 2)).max() == 0.0  # exactly symmetric
+    for k in range(S.shape[0]):
+        true_min = float(np.linalg.eigvalsh(S_raw[k]).min())
+        err = relerr(S[k], ref[k])
+        print(f"table {k}: D {S.shape[-1]} rel-Frobenius {err:.2e}; min eig {true_min:.3e}, device {mn[k]:.3e}, "
+              f"bound {min_eig_bound(S_raw[k]):.2e}, repaired {bool(rep[k])}")
+        assert err < TOL, (k, err)
+        assert bool(rep[k]) == (true_min <= 1e-6)
+        if rep[k]:
+            assert abs(mn[k] - true_min) <= min_eig_bound(S_raw[k]), (k, mn[k], true_min)
+        else:
+            assert np.isposinf(mn[k])
+    if expect_repaired is not None:
+        assert [bool(r) for r in rep] == expect_repaired
+    return S, mn, rep
+
+
+# ============================================================================================ CPU: the kernels on the emulator
+def test_emulated_singular_tables_one_padded_tile_batch_stride(emul):
+    X = tables(2, 30, 40, seed=31)  # N < D: singular; D = 40 in one padded tile of 64; two tables
+    check_against_oracle(emul, X, "cpu", expect_repaired=[True, True])
+    Xn = ocov.normalize_min_max(X)
+    S0 = run_wide(emul, Xn, "cpu", normalize=False, eval_offset=0.25, repair=True)  # normalize = 0 on the normalised table; another offset
+    S1 = run_wide(emul, X, "cpu", normalize=True, repair=False)
+    ref0, ref1 = ocov.get_covariance(Xn, offset=0.25), ocov.empirical_cov(Xn)
+    for k in range(2):
+        assert relerr(S0[k], ref0[k]) < TOL and relerr(S1[k], ref1[k]) < TOL
+
+
+def test_emulated_two_block_columns_ragged_no_repair(emul):
+    """D = 70: two block columns, so the factorisation at the threshold runs the left-looking update; N = 200 and D = 70 are ragged
+    against the 32-row chunks and the 64-column tiles.  Uniform columns: well conditioned, so no repair and S is the plain covariance."""
+    X = np.random.default_rng(32).random((1, 200, 70))
+    S, mn, rep = check_against_oracle(emul, X, "cpu", expect_repaired=[False])
+    S_raw = ocov.empirical_cov(ocov.normalize_min_max(X))
+    assert relerr(S[0], S_raw[0]) < TOL  # untouched: no shift on the diagonal
+    S0 = run_wide(emul, X, "cpu", normalize=False, repair=False)
+    assert relerr(S0[0], ocov.empirical_cov(X)[0]) < TOL
+
+
+def test_emulated_two_block_columns_singular(emul):
+    """The bisection itself across two block columns: rank 60 of D = 70 (every factorisation breaks down in the second block column or
+    completes there)."""
+    check_against_oracle(emul, tables(1, 90, 70, seed=33, rank=60), "cpu", expect_repaired=[True])
+
+
+@pytest.mark.parametrize("D,dup", [(70, (69, 0)), (130, (129, 70)), (130, (100, 3))])
+def test_emulated_breakdown_in_a_later_block_column(emul, D, dup):
+    """A well-conditioned table with one column repeated: the covariance is singular, and the pivot that shows it lies in the second or
+    third block column -- behind the left-looking update and the solves of the panels before it (two and three block columns)."""
+    X = np.random.default_rng(34).random((1, 90, D))
+    X[0, :, dup[0]] = X[0, :, dup[1]]
+    check_against_oracle(emul, X, "cpu", expect_repaired=[True])
+
+
+def near_threshold_tables(N, D, seed=9):
+    """As test_repair_decision_near_the_threshold_follows_fp64 builds its D = 6 tables: smallest eigenvalue of the covariance ~ eps."""
+    rng = np.random.default_rng(seed)
+    B = rng.random((N, D))
+    tabs = []
+    for eps in (3e-7, 9e-7, 1.1e-6, 3e-6, 2e-5):
+        Xc = B - B.mean(0)
+        U, s, Vt = np.linalg.svd(Xc, full_matrices=False)
+        s[-1] = np.sqrt(eps * N)
+        tabs.append(U @ np.diag(s) @ Vt + B.mean(0))
+    return tabs
+
+
+def test_emulated_repair_decision_near_the_threshold_needs_no_host(emul, monkeypatch):
+    """Both sides of the reference's threshold of 1e-6 at D = 40, through main's routing (the library's eigensolver limit lowered so
+    that D = 40 counts as wide): the device takes the reference's branch each time, and no fp64 eigvalsh runs on the host."""
+    from uglad_amd import main
+    from uglad_amd.utils import prepare_data as pd_
+
+    tabs = near_threshold_tables(64, 40)
+    S_host = pd_.get_covariance(tabs, offset=0.1)
+    S_raw = ocov.empirical_cov(np.stack(tabs))
+    monkeypatch.setattr(emul, "max_eig_dim", 32)
+
+    def no_eigvalsh(*a, **k):
+        raise AssertionError("host re-decision on the wide path")
+
+    monkeypatch.setattr(np.linalg, "eigvalsh", no_eigvalsh)
+    with main.device_covariance(True):
+        S_dev = main._covariance(tabs, 0.1).numpy()
+    shifted_host = [bool(S_host[k][0, 0] - S_raw[k][0, 0] > 0.05) for k in range(5)]
+    shifted_dev = [bool(S_dev[k][0, 0] - S_raw[k][0, 0] > 0.05) for k in range(5)]
+    assert shifted_host == shifted_dev == [True, True, False, False, False]
+    for a, b in zip(S_dev, S_host):
+        assert relerr(a, b) < TOL
+
+
+def test_emulated_argument_errors_and_nan_column(emul):
+    from uglad_amd._lib import UgladError
+
+    with pytest.raises(UgladError):
+        emul.covariance_wide(torch.zeros(1, 2, emul.max_dim + 1, dtype=torch.float64))
+    with pytest.raises(UgladError):
+        emul.covariance_wide(torch.zeros(1, 4, 8))  # fp32 tables belong to lib.covariance
+    X = torch.zeros(1, 4, 8, dtype=torch.float64)
+    wsp = torch.empty(int(emul._dll.uglad_covariance_wide_workspace_floats(1, 8)), dtype=torch.float32)
+    with pytest.raises(UgladError, match="NULL"):  # null S
+        emul._call("uglad_covariance_wide", ctypes.c_void_p(X.data_ptr()), 1, 4, 8, 0, 0.1, None, None, emul._p(wsp))
+    with pytest.raises(UgladError, match="mode"):
+        S = torch.empty(1, 8, 8)
+        emul._call("uglad_covariance_wide", ctypes.c_void_p(X.data_ptr()), 1, 4, 8, 2, 0.1, emul._p(S), None, emul._p(wsp))
+    assert emul._dll.uglad_covariance_wide_workspace_floats(0, 8) < 0 and emul._dll.uglad_covariance_wide_workspace_floats(1, 0) < 0
+    with pytest.raises(UgladError):
+        emul.covariance(torch.zeros(1, 4, 300), repair=False)  # the fp32 front-end keeps refusing D > max_eig_dim
+    # a constant column under normalize = 1: the NaN row and column of the reference, the rest untouched
+    Xc = np.random.default_rng(0).standard_normal((1, 30, 8))
+    Xc[0, :, 3] = 2.5
+    S = run_wide(emul, Xc, "cpu", normalize=True, repair=False)
+    ref = ocov.empirical_cov(ocov.normalize_min_max(Xc))
+    assert np.isnan(S[0, 3, :]).all() and np.isnan(S[0, :, 3]).all() and np.isnan(ref[0, 3, :]).all()
+    ok = np.isfinite(ref[0])
+    assert np.isfinite(S[0][ok]).all() and relerr(S[0][ok], ref[0][ok]) < TOL
+
+
+# ============================================================================================ GPU
+WIDE = ["widecov_k2_n40_d288_singular", "widecov_k1_n97_d320", "widecov_k1_n400_d300_rank250"]
+
+
+def load_golden(name):
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    X = g["X"]
+    K, _, D = X.shape
+    iu = np.triu_indices(D)
+    S = np.zeros((K, D, D))
+    S[:, iu[0], iu[1]] = g["S_triu"]
+    S[:, iu[1], iu[0]] = g["S_triu"]  # (the reference's matrices are symmetric to the bit: make_widecov_goldens.py asserts it)
+    return X, S, float(g["offset"])
+
+
+def test_wide_goldens_hold_what_the_generator_says():
+    for name in WIDE:
+        X, S, offset = load_golden(name)
+        assert X.dtype == np.float32 and os.path.getsize(os.path.join(GOLDEN, name + ".npz")) < 1 << 20
+        ref = ocov.get_covariance(ocov.normalize_min_max(X), offset=offset)  # (the restatement agrees with the real reference here too)
+        assert relerr(ref, S) < 1e-9
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", WIDE)
+def test_gpu_matches_reference_goldens(name):
+    from uglad_amd import _lib
+
+    X, S_ref, offset = load_golden(name)
+    S, mn, rep = run_wide(_lib.get_lib(), X, "cuda", normalize=True, eval_offset=offset, repair=True, return_min_eig=True)
+    assert np.isfinite(S).all() and np.abs(S - np.swapaxes(S, 1, 2)).max() == 0.0
+    S_raw = ocov.empirical_cov(ocov.normalize_min_max(X))
+    for k in range(S.shape[0]):
+        true_min = float(np.linalg.eigvalsh(S_raw[k]).min())
+        print(f"{name}[{k}]: rel-Frobenius vs the reference {relerr(S[k], S_ref[k]):.2e}; min eig {true_min:.3e}, device {mn[k]:.3e}, "
+              f"bound {min_eig_bound(S_raw[k]):.2e}")
+        assert relerr(S[k], S_ref[k]) < TOL
+        assert rep[k] and abs(mn[k] - true_min) <= min_eig_bound(S_raw[k])
+
+
+@pytest.mark.gpu
+def test_gpu_uniform_table_is_left_alone_and_nine_block_columns():
+    from uglad_amd import _lib
+
+    lib = _lib.get_lib()
+    X = np.random.default_rng(41).random((1, 600, 288))  # well conditioned: min eig ~9e-3, far above the threshold
+    S, mn, rep = check_against_oracle(lib, X, "cuda", expect_repaired=[False])
+    assert abs(float(np.linalg.eigvalsh(S[0].astype(np.float64)).min()) -
+               float(np.linalg.eigvalsh(ocov.empirical_cov(ocov.normalize_min_max(X))[0]).min())) < 1e-6  # no shift
+    check_against_oracle(lib, tables(1, 64, 520, seed=42), "cuda", expect_repaired=[True])  # DP = 576: nine block columns, singular
+
+
+@pytest.mark.gpu
+def test_gpu_main_routes_wide_ragged_tables_to_the_device(monkeypatch):
+    from uglad_amd import main
+    from uglad_amd.utils import prepare_data as pd_
+
+    rng = np.random.default_rng(43)
+    tabs = [rng.random((n, 288)) for n in (40, 31, 40)]
+    S_host = main._covariance(tabs, 0.1).cpu().numpy()
+
+    def no_host(*a, **k):
+        raise AssertionError("the host covariance ran under device_covariance")
+
+    monkeypatch.setattr(pd_, "get_covariance", no_host)
+    with main.device_covariance(True):
+        S_dev = main._covariance(tabs, 0.1).cpu().numpy()
+    assert S_dev.shape == (3, 288, 288)
+    for k in range(3):
+        assert relerr(S_dev[k], S_host[k].astype(np.float64)) < TOL, (k, relerr(S_dev[k], S_host[k].astype(np.float64)))
+
+
+@pytest.mark.gpu
+def test_gpu_fit_beyond_256_with_device_covariance_matches_host_path():
+    import uglad_amd
+    from uglad_amd.utils.prepare_data import get_data
+
+    X, _ = get_data(288, (0.02, 0.04), 600, 1, eig_offset=1.0, rng=11)
+    out = []
+    for dev_cov in (False, True):
+        torch.manual_seed(0)
+        est = uglad_amd.uGLAD_GL(device_covariance=dev_cov)
+        est.fit(X[0], epochs=2, lr=0.01, L=3, verbose=False)
+        out.append(est.precision_.copy())
+    assert relerr(out[1], out[0].astype(np.float64)) < 1e-4
+
+
+@pytest.mark.gpu
+def test_gpu_wide_covariance_can_be_captured_into_the_callers_graph():
+    """Nothing in the ~280 launches at D = 288 allocates, synchronises or reads back: enqueued on a side stream under capture and replayed
+    once, the call gives the bits of the eager call."""
+    from uglad_amd import _lib
+
+    lib = _lib.get_lib()
+    X = torch.from_numpy(tables(2, 40, 288, seed=44)).cuda()
+    K, N, D = X.shape
+    S = torch.empty(K, D, D, dtype=torch.float32, device="cuda")
+    mn = torch.empty(K, dtype=torch.float64, device="cuda")
+    wsp = torch.empty(int(lib._dll.uglad_covariance_wide_workspace_floats(K, D)), dtype=torch.float32, device="cuda")
+
+    def call():
+        lib._call("uglad_covariance_wide", ctypes.c_void_p(X.data_ptr()), K, N, D, 1, 0.1, lib._p(S), ctypes.c_void_p(mn.data_ptr()),
+                  lib._p(wsp))
+
+    call()
+    torch.cuda.synchronize()
+    plain = (S.clone(), mn.clone())
+    assert torch.isfinite(plain[1]).all()  # both tables are singular: repaired
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        call()  # warm-up on the capture stream
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            call()
+    S.zero_(), mn.zero_(), wsp.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(S, plain[0]) and torch.equal(mn, plain[1])

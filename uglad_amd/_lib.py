@@ -59,6 +59,9 @@ _SIGS = {
     "uglad_symeig": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_covariance": ([_c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_float_p, _c_float_p,
                           _c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_covariance_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_covariance_wide": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_float_p,
+                               ctypes.c_void_p, _c_float_p, ctypes.c_void_p], ctypes.c_int),
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
@@ -299,6 +302,30 @@ class HipLib:
             if not repair:
                 raise UgladError("return_min_eig needs repair=True (the eigenvalues come from the repair's solver run)")
             return S, scratch[K * D * D:].reshape(K, D)[:, 0].clone()
+        return S
+
+    def covariance_wide(self, X64, normalize: bool = False, eval_offset: float = 0.1, repair: bool = True,
+                        return_min_eig: bool = False):
+        """(K,N,D) FLOAT64 tables on the device -> (K,D,D) fp32 covariances for every D <= max_dim (uglad_covariance_wide): fp64
+        throughout, the repair decided by a Cholesky bisection instead of an eigensolver.  With `return_min_eig` also the (K,) fp64
+        smallest eigenvalues before the repair (+inf for a table that needed none) and the (K,) bool mask of the repaired tables."""
+        if X64.dtype != torch.float64 or not X64.is_contiguous() or X64.dim() != 3:
+            raise UgladError("covariance_wide takes a contiguous (K, N, D) float64 tensor")
+        if self.require_gpu and not X64.is_cuda:
+            raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
+        if return_min_eig and not repair:
+            raise UgladError("return_min_eig needs repair=True (the eigenvalue comes from the repair's bisection)")
+        K, N, D = X64.shape
+        n = int(self._dll.uglad_covariance_wide_workspace_floats(int(K), int(D)))
+        if n < 0:
+            self._check("uglad_covariance_wide_workspace_floats", n)
+        wsp = torch.empty(n, dtype=torch.float32, device=X64.device)  # must outlive the enqueue
+        S = torch.empty(K, D, D, dtype=torch.float32, device=X64.device)
+        mn = torch.empty(K, dtype=torch.float64, device=X64.device) if repair else None
+        self._call("uglad_covariance_wide", ctypes.c_void_p(X64.data_ptr()), K, N, D, int(bool(normalize)), float(eval_offset),
+                   self._p(S), ctypes.c_void_p(mn.data_ptr()) if repair else None, self._p(wsp))
+        if return_min_eig:
+            return S, mn, ~torch.isinf(mn)
         return S
 
     def conditional_mean(self, precision, mean, observed, values, clip01: bool = False):

@@ -39,6 +39,7 @@ namespace uglad {
 #include "wide_bwd.h"
 #include "wide_fwd.h"
 #include "wide_ns.h"
+#include "cov_wide.h"
 #endif
 #include "theta0.h"
 #include "loss.h"

@@ -54,6 +54,36 @@ int uglad_covariance(const float* X, int K, int N, int D, int normalize, float e
   return launch_status();
 }
 
+int uglad_covariance_wide_workspace_floats(int K, int D) {
+  if (K < 1 || K > 65535 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  const size_t n = cov_wide_layout(nullptr, D).total_floats(K);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+
+int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, double eval_offset, float* S_out, double* min_eig_out,
+                          float* workspace, uglad_stream_t stream) {
+  if (!X || !S_out || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (uglad_covariance_wide_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
+  if (normalize != 0 && normalize != 1) return UGLAD_E_MODE;
+  hipStream_t st = (hipStream_t)stream;
+  const CovWideLayout l = cov_wide_layout(workspace, D);
+  const int nt = l.DP / kCovwT;
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X, N, D, normalize, l.view);
+  hipLaunchKernelGGL(covw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, l.view, S_out);
+  if (!min_eig_out) return launch_status();  // no repair
+  // the test at the threshold, then the bisection: tables that are done (or whose factorisation has broken down) cost empty launches
+  for (int step = 0; step <= kCovwSteps; ++step) {
+    hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, l.view);
+    for (int j = 0; j < nt; ++j) {
+      hipLaunchKernelGGL(covw_chol_update_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
+      hipLaunchKernelGGL(covw_chol_panel_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
+    }
+  }
+  hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, kCovwSteps, D, l.view);
+  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, l.view, S_out, min_eig_out);
+  return launch_status();
+}
+
 
 #ifdef UGLAD_PHASE_EXIT
 int uglad_diag_set_exit(int at) {  // (development build: see glad_device.h)

@@ -238,3 +238,22 @@ static NsLayout ns_layout(float* workspace, int M, int D) {
   l.Gh = l.W ? l.W + 2 * kNsSlabs * l.dslab : nullptr;
   return l;
 }
+
+// ---- workspace of the wide covariance front-end (cov_wide.h), per table, in DOUBLES (the buffer is 8-byte aligned; DP = D rounded up to 64):
+//   S64   DP x DP   the covariance in fp64, row stride DP, identity in the padding; repaired in place
+//   W     DP x DP   the Cholesky factor of S64 - sigma I under test: the tiles below the block diagonal (the diagonal tiles stay unfactored)
+//   mn | scale | mu   3 DP   the column statistics
+//   CovwCtl   8   the bisection's bracket, sigma, min eig and the flags (not PD, active, repaired)
+struct CovWideLayout {
+  int DP;
+  size_t table;  // doubles per table
+  CovwView view;
+  size_t total_floats(int K) const { return 2 * (size_t)K * table; }
+};
+static CovWideLayout cov_wide_layout(float* workspace, int D) {
+  CovWideLayout l{};
+  l.DP = (D + kCovwT - 1) / kCovwT * kCovwT;
+  l.table = covw_table_doubles(l.DP);
+  l.view = CovwView{reinterpret_cast<double*>(workspace), l.table, l.DP};
+  return l;
+}

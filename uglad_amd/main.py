@@ -138,7 +138,8 @@ _DEVICE_COVARIANCE = False  # set for the duration of a fit()/predict() by uGLAD
 @contextlib.contextmanager
 def device_covariance(enabled: bool = True):
     """Within this context the drivers form the covariances (and the reference's eigenvalue repair) on the GPU
-    (`uglad_covariance`) instead of in fp64 numpy on the host (prepare_data.py:328-356)."""
+    (`uglad_covariance`, beyond the eigensolver's size `uglad_covariance_wide`) instead of in fp64 numpy on the host
+    (prepare_data.py:328-356)."""
     global _DEVICE_COVARIANCE
     saved, _DEVICE_COVARIANCE = _DEVICE_COVARIANCE, bool(enabled)
     try:
@@ -157,8 +158,13 @@ def _device_covariance_group(X: np.ndarray, eval_offset: float) -> torch.Tensor:
     The reference decides its repair from fp64 eigenvalues (prepare_data.py:343-352); the device sees fp32 eigenvalues of an
     fp32 covariance, whose absolute error is ~1e-7 ||S||.  Where the device's smallest eigenvalue lies within REPAIR_BAND of
     the threshold the decision could flip -- an O(offset) discontinuity -- so exactly those matrices (rare: nearly singular
-    with a minimum eigenvalue of ~1e-6) are re-decided from an fp64 eigvalsh on the host and corrected in place."""
+    with a minimum eigenvalue of ~1e-6) are re-decided from an fp64 eigvalsh on the host and corrected in place.
+    Tables wider than the eigensolver's size go to the fp64 front-end, which needs no such band."""
     lib = _lib.get_lib()
+    if X.shape[-1] > lib.max_eig_dim:
+        # beyond the eigensolver's size: the fp64 front-end (csrc/cov_wide.h) takes the reference's decision itself, in fp64
+        return lib.covariance_wide(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(_lib.device()), normalize=False,
+                                   eval_offset=eval_offset, repair=True)
     Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.device())
     S, mn = lib.covariance(Xd, normalize=False, eval_offset=eval_offset, repair=True, return_min_eig=True)
     mn = mn.cpu().numpy().astype(np.float64)
@@ -181,7 +187,7 @@ def _covariance(Xb, eval_offset):
     differ in length) and every group of equal shape is one launch of the device front-end."""
     if _DEVICE_COVARIANCE:
         tables = [np.asarray(x) for x in Xb]
-        max_dim = _lib.get_lib().max_eig_dim  # (the device front-end's kernels: wider tables take the host path below)
+        max_dim = _lib.get_lib().max_dim  # (what the cell covers; wider tables take the host path below, and fail at the cell)
         if tables and all(t.ndim == 2 and t.shape[1] <= max_dim and t.dtype != object for t in tables):
             groups = {}
             for i, t in enumerate(tables):
