@@ -8,7 +8,8 @@
  *
  * Conventions
  *  - every pointer is a DEVICE pointer to a caller-owned, contiguous, row-major fp32 buffer; sizes are explicit (the one exception:
- *    uglad_covariance_wide reads its tables, and returns its eigenvalues, in fp64);
+ *    uglad_covariance_wide reads its tables, and returns its eigenvalues, in fp64, and uglad_conditional_mean_wide is fp64 but for
+ *    its mask and cond_cov);
  *  - `stream` is the hipStream_t the work is enqueued on (pass torch's current stream); nothing synchronises;
  *  - no allocation or free of device memory; the library never keeps a device pointer after returning; entry points that
  *    run the eigensolver take a caller-owned `workspace` of uglad_workspace_floats(M, D) floats;
@@ -82,7 +83,8 @@ int uglad_set_wide_mode(int mode);
  * Gershgorin UPPER BOUND of the condition number; Theta_0 and the loss's logdet / inverse use an L D L^T factorisation without
  * pivoting (torch.logdet's rules from the signs of D: finite for an even number of negative eigenvalues, NaN for an odd one; a zero
  * pivot gives NaN where a singular matrix gives -inf in torch).  The entry points of the path (init_theta, cell_fwd / cell_bwd, loss_*, glad_forward* / glad_backward*) take every
- * D <= uglad_max_dim(), and so does the covariance front-end through uglad_covariance_wide; uglad_symeig, uglad_cell_fwd_stage2,
+ * D <= uglad_max_dim(), and so do the covariance front-end through uglad_covariance_wide and the conditional Gaussian through
+ * uglad_conditional_mean_wide; uglad_symeig, uglad_cell_fwd_stage2,
  * uglad_tridiagonalize, uglad_covariance (the fp32 front-end, whose repair runs the eigensolver), uglad_conditional_mean and
  * uglad_support_metrics stay at uglad_max_eig_dim().  A call on this path takes at most 21845 matrices (UGLAD_E_DIM beyond: matrix x
  * product, up to three products, share one grid dimension).
@@ -319,6 +321,24 @@ int uglad_tridiagonalize(const float* A0, const float* A1, const float* lam, flo
 int uglad_conditional_mean(const float* precision, const float* mean, const float* observed, const float* values,
                            float* full_mean, float* cond_cov, float* log_pdf, float* scratch, float* workspace, int K, int D,
                            int clip01, uglad_stream_t stream);
+
+/* The same conditional Gaussian for every D <= uglad_max_dim() -- what the cell covers -- in fp64 and without the eigensolver
+ * (csrc/after_wide.h; replaces conditional_gaussian_with_probabilities + compute_map_estimate, main.py:1176-1260): the masked precision
+ * matrix (P on the (unobserved, unobserved) block, identity elsewhere) is factored by the blocked Cholesky of uglad_covariance_wide, many
+ * workgroups per problem; L^-1 by block forward substitution gives the solve (with one step of refinement), the inverse and the
+ * log-determinant.  precision, mean, values, full_mean and log_pdf are FP64 DEVICE pointers (as for uglad_covariance_wide: the only
+ * rounding left is the fp32 store of cond_cov); observed is fp32, non-zero where the coordinate is observed.
+ *   cond_cov (K,D,D) fp32 or NULL: exactly symmetric; NULL skips the product (compute_map_estimate needs none);
+ *   log_pdf (K) or NULL.
+ * L_uu not positive definite (a pivot <= 0 or NaN): log_pdf = NaN, the unobserved entries of full_mean and the (u, u) block of cond_cov
+ * are NaN, observed entries pass through, the other problems of the batch are unaffected (the reference's multivariate_normal.pdf
+ * raises there).  3 ceil(D / 64) + 8 launches in one chain, no host readback.  workspace:
+ * uglad_conditional_mean_wide_workspace_floats(K, D) floats, 8-byte aligned (UGLAD_E_NULL otherwise).  K <= 65535.  Errors as
+ * uglad_covariance_wide; the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+int uglad_conditional_mean_wide_workspace_floats(int K, int D);
+int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,
+                                double* full_mean, float* cond_cov, double* log_pdf, float* workspace, int K, int D, int clip01,
+                                uglad_stream_t stream);
 
 /* After the path.  Partial correlations rho_ij = -p_ij / sqrt(p_ii p_jj) from the upper triangle, mirrored,
  * ones on the diagonal (get_partial_correlations, main.py:796-821), K matrices at once. */

@@ -65,6 +65,8 @@ _SIGS = {
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "uglad_conditional_mean_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_conditional_mean_wide": ([ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_partial_correlations": ([_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_support_metrics": ([_c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
                               ctypes.c_int),
@@ -337,6 +339,31 @@ class HipLib:
         wsp = self.workspace(K, D, precision)
         self._call("uglad_conditional_mean", self._p(precision), self._p(mean), self._p(observed), self._p(values),
                    self._p(full_mean), self._p(cond_cov), self._p(log_pdf), self._p(scratch), self._p(wsp), K, D, int(bool(clip01)))
+        return full_mean, cond_cov, log_pdf
+
+    def conditional_mean_wide(self, P64, mean64, observed, values64, clip01: bool = False, want_cov: bool = True):
+        """uglad_conditional_mean_wide, every D <= max_dim: (K,D,D), (K,D) FLOAT64, (K,D) fp32 mask, (K,D) FLOAT64 -> full_mean (K,D)
+        float64, cond_cov (K,D,D) fp32 (None without `want_cov`: the product is skipped), log_pdf (K) float64.  A problem whose L_uu is
+        not positive definite comes back with NaN in log_pdf, in the unobserved entries of full_mean and in the (u, u) block of cond_cov."""
+        for a, shape in ((P64, 3), (mean64, 2), (values64, 2)):
+            if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() != shape:
+                raise UgladError("conditional_mean_wide takes contiguous float64 tensors (K, D, D), (K, D), (K, D) and a float32 mask")
+            if self.require_gpu and not a.is_cuda:
+                raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
+        K, D, _ = P64.shape
+        if P64.shape[2] != D or tuple(mean64.shape) != (K, D) or tuple(values64.shape) != (K, D) or tuple(observed.shape) != (K, D):
+            raise UgladError("conditional_mean_wide: shapes (K, D, D), (K, D), (K, D), (K, D)")
+        n = int(self._dll.uglad_conditional_mean_wide_workspace_floats(int(K), int(D)))
+        if n < 0:
+            self._check("uglad_conditional_mean_wide_workspace_floats", n)
+        dev = P64.device
+        wsp = torch.empty(n, dtype=torch.float32, device=dev)  # must outlive the enqueue
+        full_mean = torch.empty(K, D, dtype=torch.float64, device=dev)
+        log_pdf = torch.empty(K, dtype=torch.float64, device=dev)
+        cond_cov = torch.empty(K, D, D, dtype=torch.float32, device=dev) if want_cov else None
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        self._call("uglad_conditional_mean_wide", vp(P64), vp(mean64), self._p(observed), vp(values64), vp(full_mean), self._p(cond_cov),
+                   vp(log_pdf), self._p(wsp), K, D, int(bool(clip01)))
         return full_mean, cond_cov, log_pdf
 
     def partial_correlations(self, precision):

@@ -22,6 +22,8 @@
 //                            workgroup alone raises the flag on a pivot that is <= 0 or NaN (no atomics).  L(j, j) itself is never
 //                            stored: no later launch reads it, and the workgroups of THIS launch are still reading the tile it would replace
 //                         Every launch returns at once for a table that is flagged or inactive (the gated empties of ns_ldl_phase_kernel).
+//                         covw_chol_panel_kernel<true> (after_wide.h, sigma = 0): the diagonal tile's workgroup also runs the solve, on the
+//                         identity, and writes L(j, j)^-T and the 64 log-pivots into slabs of their own behind the control block
 //   covw_repair_kernel    active tables: the diagonal of S64 += offset - min eig, the diagonal of S_out rewritten from it (one rounding)
 //
 // Every sum has a fixed order (rows over waves combined in wave order, the k-ordered fma chain of the MFMA), so results are bit-reproducible.
@@ -58,6 +60,10 @@ struct CovwView {
   __host__ __device__ double* w(int t) const { return s64(t) + (size_t)DP * DP; }
   __host__ __device__ double* stats(int t) const { return w(t) + (size_t)DP * DP; }  // mn | scale | mu, DP each
   __host__ __device__ CovwCtl* ctl(int t) const { return reinterpret_cast<CovwCtl*>(stats(t) + 3 * (size_t)DP); }
+  // behind the control block, only in the layout of the factorisation's second client (after_wide.h; covw_chol_panel_kernel<true>):
+  // the transposed inverse of the factor, then the logarithms of the DP pivots
+  __host__ __device__ double* inv_t(int t) const { return stats(t) + 3 * (size_t)DP + 8; }
+  __host__ __device__ double* log_pivot(int t) const { return inv_t(t) + (size_t)DP * DP; }
 };
 __host__ __device__ constexpr size_t covw_table_doubles(int DP) { return 2 * (size_t)DP * DP + 3 * (size_t)DP + 8; }
 
@@ -292,6 +298,7 @@ __global__ __launch_bounds__(kWThreads) void covw_chol_update_kernel(int j, Covw
 // right-looking, one barrier per column; the column stays unscaled until the end so that every thread forms l_rc = a_rc / sqrt(a_cc) from the
 // same bits -- and then solves its own tile X L(j, j)^T = W(i, j) column by column.  A pivot that is <= 0 or NaN ends the factorisation in
 // every workgroup alike; the diagonal tile's workgroup raises the flag.  W(j, j) is only read here (all workgroups of the launch load it).
+template <bool kKeepDiag>
 __global__ __launch_bounds__(kWThreads) void covw_chol_panel_kernel(int j, CovwView v) {
   __shared__ double s_d[kCovwT * kCovwLdt], s_t[kCovwT * kCovwLdt], s_inv[kCovwT];
   const int t = blockIdx.y;
@@ -324,7 +331,12 @@ __global__ __launch_bounds__(kWThreads) void covw_chol_panel_kernel(int j, CovwV
     if (blockIdx.x == 0 && tid == 0) ctl->notpd = 1;
     return;
   }
-  if (blockIdx.x == 0) return;  // (the diagonal tile's workgroup: its part was the decision)
+  const bool diag = blockIdx.x == 0;
+  if (diag) {
+    if constexpr (!kKeepDiag) return;  // (the diagonal tile's workgroup: its part was the decision)
+    // kKeepDiag: the solve below on the identity instead of the tile gives L(j, j)^-T
+    for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) s_t[(idx >> 6) * kCovwLdt + (idx & 63)] = (idx >> 6) == (idx & 63) ? 1.0 : 0.0;
+  }
   __syncthreads();
   // X L^T = T: x_rc = (t_rc - sum_{p < c} x_rp l_cp) / l_cc, with l_qc = s_d[q][c] inv_c and l_cc = 1 / inv_c
   for (int c = 0; c < kCovwT; ++c) {
@@ -335,6 +347,17 @@ __global__ __launch_bounds__(kWThreads) void covw_chol_panel_kernel(int j, CovwV
     for (int q = c + 1 + ((w - c - 1) & 3); q < kCovwT; q += 4) s_t[r * kCovwLdt + q] -= x * (s_d[q * kCovwLdt + c] * inv);
   }
   __syncthreads();
+  if constexpr (kKeepDiag) {
+    if (diag) {  // into the slab of the inverse, NOT over tile (j, j) of W: the other workgroups of this launch are still reading that
+      double* Wt = v.inv_t(t);
+      for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) {
+        const int rr = idx >> 6, cc = idx & 63;
+        Wt[(size_t)(j0 + rr) * DP + j0 + cc] = cc >= rr ? s_t[rr * kCovwLdt + cc] : 0.0;
+      }
+      if (tid < kCovwT) v.log_pivot(t)[j0 + tid] = log(s_d[tid * kCovwLdt + tid]);
+      return;
+    }
+  }
   for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) {
     const int rr = idx >> 6, cc = idx & 63;
     W[(size_t)(i0 + rr) * DP + j0 + cc] = s_t[rr * kCovwLdt + cc];

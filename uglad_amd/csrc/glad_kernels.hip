@@ -40,6 +40,7 @@ namespace uglad {
 #include "wide_fwd.h"
 #include "wide_ns.h"
 #include "cov_wide.h"
+#include "after_wide.h"
 #endif
 #include "theta0.h"
 #include "loss.h"

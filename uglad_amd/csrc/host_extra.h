@@ -76,7 +76,7 @@ int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, d
     hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, l.view);
     for (int j = 0; j < nt; ++j) {
       hipLaunchKernelGGL(covw_chol_update_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
-      hipLaunchKernelGGL(covw_chol_panel_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
+      hipLaunchKernelGGL(covw_chol_panel_kernel<false>, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
     }
   }
   hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, kCovwSteps, D, l.view);
@@ -134,6 +134,42 @@ int uglad_conditional_mean(const float* precision, const float* mean, const floa
     hipLaunchKernelGGL((map_solve_kernel<decltype(nt)::value>), dim3(K), dim3(kThreads), 0, st, precision, mean, observed, values,
                                     scratch, full_mean, cond_cov, log_pdf, workspace, D, clip01);
   });
+  return launch_status();
+}
+
+int uglad_conditional_mean_wide_workspace_floats(int K, int D) {
+  if (K < 1 || K > 65535 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  const size_t n = after_wide_layout(nullptr, D).total_floats(K);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+
+int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,
+                                double* full_mean, float* cond_cov, double* log_pdf, float* workspace, int K, int D, int clip01,
+                                uglad_stream_t stream) {
+  if (!precision || !mean || !observed || !values || !full_mean || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (uglad_conditional_mean_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const AfterWideLayout l = after_wide_layout(workspace, D);
+  const AfterwView v = l.view;
+  const AfterwIn in{precision, mean, observed, values};
+  const int nt = l.DP / kCovwT;
+  const dim3 rows(nt, K), tiles(nt, nt, K), wg(kWThreads);
+  hipLaunchKernelGGL(afterw_prepare_kernel, tiles, wg, 0, st, in, D, v);
+  hipLaunchKernelGGL(afterw_rhs_kernel, rows, dim3(64), 0, st, observed, D, v);
+  for (int j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(covw_chol_update_kernel, dim3(nt - j, K), wg, 0, st, j, v.c);
+    hipLaunchKernelGGL(covw_chol_panel_kernel<true>, dim3(nt - j, K), wg, 0, st, j, v.c);
+  }
+  for (int i = 1; i < nt; ++i) hipLaunchKernelGGL(afterw_subst_kernel, dim3(i, K), wg, 0, st, i, v);
+  // y = W^T (W r); y += W^T (W (r - A y))
+  using V = AfterwView;
+  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwLower, (int)V::kR, (int)V::kT, 0, v);
+  hipLaunchKernelGGL(afterw_matvec_kernel<true>, rows, wg, 0, st, (int)kAfterwUpper, (int)V::kT, (int)V::kY, 0, v);
+  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwResidual, (int)V::kY, (int)V::kRes, 0, v);
+  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwLower, (int)V::kRes, (int)V::kT, 0, v);
+  hipLaunchKernelGGL(afterw_matvec_kernel<true>, rows, wg, 0, st, (int)kAfterwUpper, (int)V::kT, (int)V::kY, 1, v);
+  if (cond_cov) hipLaunchKernelGGL(afterw_cov_kernel, tiles, wg, 0, st, observed, D, v, cond_cov);
+  hipLaunchKernelGGL(afterw_finish_kernel, rows, wg, 0, st, in, D, clip01, v, full_mean, log_pdf);
   return launch_status();
 }
 

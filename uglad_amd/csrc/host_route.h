@@ -257,3 +257,27 @@ static CovWideLayout cov_wide_layout(float* workspace, int D) {
   l.view = CovwView{reinterpret_cast<double*>(workspace), l.table, l.DP};
   return l;
 }
+
+// ---- workspace of the wide conditional Gaussian (after_wide.h), per problem, in DOUBLES (8-byte aligned; DP = D rounded up to 64): the
+// factorisation's own layout first, so that its kernels serve both clients --
+//   A     DP x DP   the masked precision matrix, identity on the observed coordinates and in the padding
+//   L     DP x DP   its Cholesky factor: the tiles below the block diagonal
+//   r | y | t   3 DP   right-hand side, solution, intermediate (where the covariance keeps its column statistics)
+//   CovwCtl   8   only the "not PD" flag is live (sigma = 0, always active)
+// -- and behind it
+//   Wt    DP x DP   L^-T, block upper triangular
+//   log pivots | residual   2 DP
+//   parts of r   DP / 64 x DP   one row per block column of A
+struct AfterWideLayout {
+  int DP;
+  size_t problem;  // doubles per problem
+  AfterwView view;
+  size_t total_floats(int K) const { return 2 * (size_t)K * problem; }
+};
+static AfterWideLayout after_wide_layout(float* workspace, int D) {
+  AfterWideLayout l{};
+  l.DP = (D + kCovwT - 1) / kCovwT * kCovwT;
+  l.problem = afterw_problem_doubles(l.DP);
+  l.view = AfterwView{CovwView{reinterpret_cast<double*>(workspace), l.problem, l.DP}};
+  return l;
+}

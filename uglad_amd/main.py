@@ -775,20 +775,44 @@ def get_partial_correlations(precision):
     return rho
 
 
-def conditional_gaussian_batch(precision, mean, observed_mask, observed_values, clip01: bool = False):
-    """K conditional-Gaussian problems on the device (uglad_conditional_mean): precision (K,D,D), mean (K,D), observed_mask (K,D)
-    bool, observed_values (K,D) (read where observed) -> full_mean (K,D), cond_cov (K,D,D) (L_uu^-1 on the unobserved block,
-    identity elsewhere), log_pdf (K) -- torch tensors on the device."""
+# Smallest D > max_eig_dim that goes to uglad_conditional_mean_wide; below it (and above max_eig_dim) the host formulation would run.  0: the
+# whole range goes to the device.  scripts/after_wide_probe.py times both sides; a range where the host wins end to end belongs here.
+WIDE_CONDITIONAL_MIN_DIM = 0
+
+
+def conditional_gaussian_batch(precision, mean, observed_mask, observed_values, clip01: bool = False, want_cov: bool = True):
+    """K conditional-Gaussian problems on the device: precision (K,D,D), mean (K,D), observed_mask (K,D) bool, observed_values (K,D)
+    (read where observed) -> full_mean (K,D), cond_cov (K,D,D) (L_uu^-1 on the unobserved block, identity elsewhere), log_pdf (K) --
+    fp32 torch tensors on the device.  D <= max_eig_dim: uglad_conditional_mean (the path's eigensolver, fp32); beyond, up to max_dim:
+    uglad_conditional_mean_wide (fp64 Cholesky, many workgroups per problem; `want_cov=False` skips the inverse and returns None for it)."""
+    full, cov, logp = _conditional_gaussian_device(precision, mean, observed_mask, observed_values, clip01, want_cov)
+    return full.to(torch.float32), cov, logp.to(torch.float32)
+
+
+def _conditional_gaussian_device(precision, mean, observed_mask, observed_values, clip01, want_cov):
+    """conditional_gaussian_batch in the precision the entry point computes in: full_mean and log_pdf are fp64 beyond max_eig_dim."""
     dev = _lib.device()
-    f = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32).to(dev).contiguous() if not torch.is_tensor(a) \
-        else a.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    if np.shape(precision)[-1] > _lib.get_lib().max_eig_dim:
+    lib = _lib.get_lib()
+
+    def to(a, dtype):
+        # a host array is converted on the host and uploaded once; a device tensor is converted on the device
+        if torch.is_tensor(a):
+            return a.detach().to(device=dev, dtype=dtype).contiguous()
+        return torch.as_tensor(np.asarray(a), dtype=dtype).to(dev).contiguous()
+
+    D = np.shape(precision)[-1]
+    if D <= lib.max_eig_dim:
+        f = lambda a: to(a, torch.float32)  # noqa: E731
+        return lib.conditional_mean(f(precision), f(mean), f(observed_mask), f(observed_values), clip01=clip01)
+    if D > lib.max_dim or D < WIDE_CONDITIONAL_MIN_DIM:
         return _conditional_gaussian_host(precision, mean, observed_mask, observed_values, clip01, dev)
-    return _lib.get_lib().conditional_mean(f(precision), f(mean), f(observed_mask), f(observed_values), clip01=clip01)
+    f = lambda a: to(a, torch.float64)  # noqa: E731
+    return lib.conditional_mean_wide(f(precision), f(mean), to(observed_mask, torch.float32), f(observed_values), clip01=clip01,
+                                     want_cov=want_cov)
 
 
 def _conditional_gaussian_host(precision, mean, observed_mask, observed_values, clip01, dev):
-    """D beyond the device solver of uglad_conditional_mean (the path's eigensolver, D <= 256): the reference's own formulation on the host in
+    """D beyond what the device covers (uglad_conditional_mean_wide, D <= max_dim = 2048): the reference's own formulation on the host in
     float64 (ref main.py:1176-1227: mean_u - L_uu^-1 L_uo (x_o - mean_o), conditional covariance L_uu^-1, the density at the MAP point), returned
     in the layout of the device entry point (full mean; L_uu^-1 on the unobserved block, identity elsewhere; log density)."""
     to64 = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)  # noqa: E731
@@ -817,7 +841,8 @@ def _conditional_gaussian_host(precision, mean, observed_mask, observed_values, 
 def conditional_gaussian_with_probabilities(precision, mean, observed_idx, observed_values):
     """Conditional mean, conditional covariance and density at the MAP point of a Gaussian given observed coordinates
     (ref main.py:1176-1227, same arguments and return values): (full_mean (n,), conditional_cov (n_u, n_u), pdf).
-    The reference solves with scipy on the host; here the path's eigensolver does it on the device (fp32)."""
+    The reference solves with scipy on the host; here the path's eigensolver does it on the device (fp32), and beyond its size the fp64
+    Cholesky of uglad_conditional_mean_wide: the density is the exponential of its fp64 logarithm."""
     precision = np.asarray(precision)
     mean = np.asarray(mean, dtype=np.float64)
     n = len(mean)
@@ -826,7 +851,7 @@ def conditional_gaussian_with_probabilities(precision, mean, observed_idx, obser
     mask[observed_idx] = 1.0
     vals = np.zeros(n, dtype=np.float64)
     vals[observed_idx] = np.asarray(observed_values, dtype=np.float64)
-    full, cov, logp = conditional_gaussian_batch(precision[None], mean[None], mask[None], vals[None])
+    full, cov, logp = _conditional_gaussian_device(precision[None], mean[None], mask[None], vals[None], False, True)
     unobs = [i for i in range(n) if mask[i] == 0.0]
     cov = cov[0].cpu().numpy().astype(np.float64)
     return full[0].cpu().numpy().astype(np.float64), cov[np.ix_(unobs, unobs)], float(np.exp(np.float64(logp[0].item())))
@@ -843,7 +868,7 @@ def compute_map_estimate(observed_nodes: dict, model_uGLAD) -> np.ndarray:
     vals = np.zeros(n, dtype=np.float64)
     vals[idx] = list(observed_nodes.values())
     full, _, _ = conditional_gaussian_batch(np.asarray(model_uGLAD.precision_)[None], np.asarray(model_uGLAD.location_)[None],
-                                            mask[None], vals[None], clip01=True)
+                                            mask[None], vals[None], clip01=True, want_cov=False)
     return full[0].cpu().numpy().astype(np.float64)
 
 
