@@ -274,7 +274,13 @@ int uglad_consensus_combine(const float* absmin, const float* signsum, int D, fl
  * Householder tridiagonalisation + divide & conquer + blocked back-transformation, the solver inside uglad_cell_fwd,
  * exported for unit tests.  U must not alias A (its slab doubles as reflector scratch).  No rescaling of the input: measured
  * on structured matrices (profiles/r04_symeig_sweep.txt) the errors are those of unit scale (<= 2.4e-6) for ||A|| from 1e-9 to
- * 1e18 and grow below (1e-4 at 1e-11: intermediate cubes of pole distances leave the fp32 range); the cell's b = S/lam - Z is O(1). */
+ * 1e18 and grow below (1e-4 at 1e-11: intermediate cubes of pole distances leave the fp32 range); the cell's b = S/lam - Z is O(1).
+ * Accuracy (max of eigenvalue error / ||A||_2 and ||A U - U diag beta||_F / ||A||_F; profiles/eigensolver_spectra.txt): <= 5e-6 for
+ * separated spectra, but there is no deflation, and a cluster of m (nearly) equal eigenvalues is spread over up to 4 * 2^-24 * m ||A||
+ * -- O(D eps ||A||): the bound is 5e-6 + 4 * 2^-24 * D, i.e. 2.0e-5 / 3.6e-5 / 6.6e-5 at D = 64 / 128 / 256.  max |U^T U - I| <= 5e-6
+ * either way.  Matrices of low rank (the constant matrix, blocks of ones next to blocks of zeros), whose tridiagonal form decays to
+ * 1e-26 of ||A||, meet the 5e-6 bound: couplings below 8 eps ||A|| are dropped rather than merged, and a column whose entries below the
+ * sub-diagonal have a norm below 3.2e-18 (absolute) gets no reflector. */
 int uglad_symeig(const float* A, float* U, float* beta, float* workspace, int M, int D, uglad_stream_t stream);
 
 /* Covariance front-end of fit() (replaces prepare_data.py:328-356 get_covariance and, with normalize = 1,

@@ -198,7 +198,7 @@ def test_symeig_every_size_up_to_64(lib):
         assert ((beta.double().sort(dim=1).values - w).abs().max(dim=1).values / w.abs().max(dim=1).values.clamp_min(1.0)).max() < 5e-6, D
 
 
-@pytest.mark.parametrize("D", [3, 16, 33, 128])
+@pytest.mark.parametrize("D", [3, 16, 33, 100, 128])
 def test_degenerate_and_nearly_degenerate_spectra_vs_fp64_oracle(lib, D):
     """Covariances whose b = S/lambda - Z has repeated or nearly repeated eigenvalues -- exactly diagonal, the identity, equicorrelation (D - 1 equal
     eigenvalues), repeated 4 x 4 blocks, AR(1), nearly diagonal, nearly the identity -- where an eigenvector-based matrix function and its

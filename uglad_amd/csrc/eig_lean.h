@@ -8,9 +8,16 @@
 //      secular equation per eigenvalue (LAPACK-style starting point, rational iteration with bracketing, origin shifted to the
 //      nearest pole so all differences are relatively accurate), Gu-Eisenstat re-derivation of z for orthogonality, and the
 //      eigenvector update Q <- Q W as block-diagonal GEMMs on the f32 MFMA.  Instead of LAPACK's deflation (data-dependent
-//      control flow) equal poles are separated by a few ulps and vanishing z components are floored at 1e-6: a backward error
-//      of O(eps ||T||) that keeps every lane on the same code path.  A merge whose coupling is below 8 eps ||.|| is skipped
-//      (sorted only);
+//      control flow) equal poles are separated by a few ulps and vanishing z components are floored at 1e-6, which keeps every
+//      lane on the same code path.  The price: a pole is pushed 4 eps max|d| past its neighbour, and the pushes of a run of
+//      coinciding poles ADD UP -- a backward error of O(eps ||T||) for separated spectra (<= 2.4e-6 measured), but up to
+//      4 * 2^-24 * m ||T|| for a cluster of m equal eigenvalues: O(D eps ||T||), 1.5e-5 / 3.1e-5 / 6.1e-5 at m = 64 / 128 / 256
+//      (measured: 0.55 - 0.7 of that).  Orthogonality is not affected (<= 1.3e-6).  tests/test_eigensolver_spectra.py pins both.
+//      A merge whose coupling rho = 2 |e| is below 8 eps max(scale of the merge, scale of the WHOLE matrix T) is skipped (sorted
+//      only).  The matrix-wide scale max(|d_i|, 2 |e_i|) matters for matrices of low rank: the tridiagonal form of the constant
+//      matrix is d = 1, D - 1, 8e-7, -9e-14, 5e-21, 1.5e-26 ..., and judged by their own scale alone the merges inside its
+//      1e-26 tail were carried out in full -- with pole distances whose cubes leave the fp32 range (NaN eigenvectors).  They
+//      are below 8 eps ||T|| many times over, so dropping their couplings is a backward error of at most 4 eps ||T|| per row;
 //   3. back-transformation Q <- H Q in blocks of 16 reflectors (compact WY).
 //
 // Steps 2 and 3 are LDS-lean: ONE DP x (DP+1) matrix (the eigenvectors Q; in LDS up to DP = 128, in the workspace beyond) plus
@@ -25,6 +32,7 @@
 //   * Gram matrix and triangular factor of a reflector block are formed by one wave in registers (lane broadcasts instead of
 //     LDS reads) and handed to the other waves through the caller's workspace.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 #include "glad_device.h"
@@ -79,6 +87,7 @@ struct LeanScratch {
   };
   float rho[DP / 2 + 1];
   int skip[DP / 2 + 1], fix[DP / 2 + 1], bmax[DP / 2 + 1];
+  int tmax;  // max(|d_i|, 2 |e_i|) of the whole tridiagonal matrix (float bits): the scale a coupling has to exceed to be merged at all
 };
 
 // ------------------------------------------------------------------------------------------------ secular equation
@@ -316,7 +325,8 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
         if (mid < n) {
           rho = 2.f * fabsf(ws.e[mid - 1]);
           const float scale = fmaxf(__int_as_float(ws.bmax[blk]), rho);
-          if (rho > 8.f * kEps * scale) {
+          // (judged against the whole matrix as well as the merge: see the header of this file.  The gap below keeps the merge's own scale.)
+          if (rho > 8.f * kEps * fmaxf(scale, __int_as_float(ws.tmax))) {
             skip = 0;
             const float z = ws.zs[p];
             ws.zh[p] = rho * z * z;
@@ -492,6 +502,13 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
   constexpr int DP = NT * 32, LD = DP + 1;
   constexpr float kEps = 5.96e-8f;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // the pole loads of secular_root_reg are unconditional and read up to 2 DP - 1 floats past the start of ds / zh (DP = 96, 160: past their
+  // end): they have to stay inside the divide & conquer vectors of the scratch, whatever the order of its members becomes
+  static_assert(offsetof(LeanScratch<DP>, ds) + 2 * DP * sizeof(float) <= offsetof(LeanScratch<DP>, act) + sizeof(int) * DP &&
+                    offsetof(LeanScratch<DP>, zh) + 2 * DP * sizeof(float) <= offsetof(LeanScratch<DP>, act) + sizeof(int) * DP &&
+                    offsetof(LeanScratch<DP>, ds) < offsetof(LeanScratch<DP>, act) && offsetof(LeanScratch<DP>, zh) < offsetof(LeanScratch<DP>, act),
+                "secular_root_reg reads ds / zh beyond the merge: keep 2 DP floats of divide & conquer scratch behind their first element");
+  if (tid == 0) ws.tmax = 0;
   for (int idx = tid; idx < DP * DP; idx += kThreads) {
     const int i = idx / DP, j = idx - i * DP;
     Q[i * LD + j] = (i == j) ? 1.f : 0.f;
@@ -499,6 +516,7 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
   __syncthreads();
   // Leaves are 2 x 2 (the last one 1 x 1 when n is odd), solved in closed form by a Jacobi rotation; the boundaries BETWEEN
   // leaves are torn: the rows on either side of boundary (2i+1 | 2i+2) give up |e_{2i+1}|.
+  if (tid < n) atomicMax(&ws.tmax, __float_as_int(fmaxf(fabsf(ws.d[tid]), (tid < n - 1) ? 2.f * fabsf(ws.e[tid]) : 0.f)));
   if (2 * tid < n) {
     const int i0 = 2 * tid, i1 = i0 + 1;
     float a = ws.d[i0];
@@ -596,7 +614,7 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
         if (mid < n) {
           rho = 2.f * fabsf(ws.e[mid - 1]);
           const float scale = fmaxf(__int_as_float(ws.bmax[blk]), rho);
-          if (rho > 8.f * kEps * scale) {
+          if (rho > 8.f * kEps * fmaxf(scale, __int_as_float(ws.tmax))) {
             skip = 0;
             const float z = ws.zs[p];
             ws.zh[p] = rho * z * z;

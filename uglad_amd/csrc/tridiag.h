@@ -16,6 +16,12 @@
 
 namespace uglad {
 
+// A column whose entries below the sub-diagonal have a squared norm of at most this gets NO reflector (tau = 0, e = the sub-diagonal entry as it
+// stands; what is dropped has norm <= 3.2e-18).  The squares of entries below 1e-19 are fp32 subnormals: their sum carries an absolute error of
+// up to n 2^-149 = 3.6e-43, so below ~1e-38 the norm is known to a few digits only, tau |v|^2 = 2 fails by as much and H is no longer orthogonal
+// (3e-3 on the constant matrix at D = 16, whose trailing columns decay 1e-7, 1e-14, 1e-21, ...).  At 1e-35 the relative error is 3.6e-8 < eps.
+constexpr float kNegligibleSig = 1e-35f;
+
 #ifdef UGLAD_STAMPS  // diagnostic build: cycles workgroup 0 spends in the reflector chain / in the sweep (scripts/stamp_cell.py)
 __device__ unsigned long long g_tstamps[4];
 __device__ unsigned long long g_twg[4096][3];  // per workgroup: start, end (s_memtime), hardware id (XCC / SE / CU)
@@ -317,7 +323,7 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
         }
         sig = wave_sum(sig);
         float beta = x0, tau1 = 0.f, sc = 0.f;
-        if (sig > 0.f) {
+        if (sig > kNegligibleSig) {
           // on the serial path of every step: hardware square root (1 ulp) and rcp + Newton divisions; tau and the scaling
           // come from the same rounded beta, so H stays orthogonal to rounding error.  (Tiny norms: library path.)
           const float nrm2 = fmaf(x0, x0, sig);

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(64) void tridiag_wave_kernel(const float* __restric
     const float dp = bcast_lane(x, p), x0 = bcast_lane(x, c0);
     float sig = wave_sum(hf == 0 ? xm * xm : 0.f);
     float beta = x0, tau = 0.f, sc = 0.f;
-    if (sig > 0.f) {  // (as tridiag.h: hardware square root, rcp + Newton divisions; tau and the scaling from the same rounded beta)
+    if (sig > kNegligibleSig) {  // (as tridiag.h: hardware square root, rcp + Newton divisions; tau and the scaling from the same rounded beta)
       const float nrm2 = fmaf(x0, x0, sig);
       if (nrm2 > 1e-30f) {
         beta = -copysignf(__builtin_amdgcn_sqrtf(nrm2), x0);
