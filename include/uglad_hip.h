@@ -83,10 +83,10 @@ int uglad_set_wide_mode(int mode);
  * Gershgorin UPPER BOUND of the condition number; Theta_0 and the loss's logdet / inverse use an L D L^T factorisation without
  * pivoting (torch.logdet's rules from the signs of D: finite for an even number of negative eigenvalues, NaN for an odd one; a zero
  * pivot gives NaN where a singular matrix gives -inf in torch).  The entry points of the path (init_theta, cell_fwd / cell_bwd, loss_*, glad_forward* / glad_backward*) take every
- * D <= uglad_max_dim(), and so do the covariance front-end through uglad_covariance_wide and the conditional Gaussian through
- * uglad_conditional_mean_wide; uglad_symeig, uglad_cell_fwd_stage2,
+ * D <= uglad_max_dim(), and so do the covariance front-end through uglad_covariance_wide, the conditional Gaussian through
+ * uglad_conditional_mean_wide and the support-recovery metrics through uglad_support_metrics_wide; uglad_symeig, uglad_cell_fwd_stage2,
  * uglad_tridiagonalize, uglad_covariance (the fp32 front-end, whose repair runs the eigensolver), uglad_conditional_mean and
- * uglad_support_metrics stay at uglad_max_eig_dim().  A call on this path takes at most 21845 matrices (UGLAD_E_DIM beyond: matrix x
+ * uglad_support_metrics stay at uglad_max_eig_dim(); the metrics report beyond it is uglad_support_metrics_wide.  A call on this path takes at most 21845 matrices (UGLAD_E_DIM beyond: matrix x
  * product, up to three products, share one grid dimension).
  * The same path is taken automatically (mode -1, the default) for FEW matrices of 128 < D <= 256 under UGLAD_SQRT_NS10, where one
  * workgroup's Householder chain is most of the spectral cell: training calls (half_out / U_out given) up to 8 matrices and
@@ -355,6 +355,21 @@ int uglad_partial_correlations(const float* precision, float* rho, int K, int D,
  * decimals).  Integer counting throughout; AUC / AUPR as sklearn defines them (ties included).  2 <= D <= uglad_max_eig_dim(). */
 int uglad_support_metrics(const float* true_theta, const float* pred_theta, double* out, int K, int D, int beta,
                           uglad_stream_t stream);
+
+/* The same 11 numbers for every 2 <= D <= uglad_max_dim() -- what the cell covers -- with many workgroups per pair (csrc/metrics_wide.h).
+ * uglad_support_metrics sweeps all E = D (D - 1) / 2 scores once per true edge from the LDS of one workgroup; here each pair's edges are
+ * sorted by score -- one 32-bit key per edge, ((bits(|pred|)) << 1) | label, a radix sort of 8 passes of 4 bits -- and the ranking metrics
+ * are prefix counts over the sorted keys: O(E) work per pass whatever the labels.  Same inputs, same definitions, all counting in
+ * integers; `!= 0` is decided on the bit pattern ((bits & 0x7fffffff) != 0: denormals and -0.0 as in numpy).  Every entry but aupr is
+ * bit-equal to uglad_support_metrics where both exist; aupr sums its T terms in another (fixed) order.  Results do not depend on K or on
+ * the pair's place in the batch.  NaN scores (sklearn raises on them) order by their bit pattern, above every finite score: the call
+ * terminates and returns what that order gives.  4 + 3 * 8 launches in one chain, no host readback.  workspace:
+ * uglad_support_metrics_wide_workspace_floats(K, D) floats (two key buffers of E words and the sort's tables per pair), 8-byte aligned
+ * (UGLAD_E_NULL otherwise).  K <= 65535.  Errors as uglad_conditional_mean_wide; the workspace size is negative (UGLAD_E_DIM) on bad
+ * arguments (D < 2 among them) or beyond 2^31 - 1 floats. */
+int uglad_support_metrics_wide_workspace_floats(int K, int D);
+int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta, double* out, float* workspace, int K, int D, int beta,
+                               uglad_stream_t stream);
 
 /* The same decomposition by two-sided cyclic Jacobi (round-robin ordering, Rutishauser rotations): slower, independent of
  * the divide & conquer solver; beta comes back unsorted.  Cross-check only. */

@@ -70,6 +70,9 @@ _SIGS = {
     "uglad_partial_correlations": ([_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_support_metrics": ([_c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
                               ctypes.c_int),
+    "uglad_support_metrics_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_support_metrics_wide": ([_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p], ctypes.c_int),
     "uglad_set_wide_mode": ([ctypes.c_int], ctypes.c_int),
     "uglad_glad_backward_wrt_s": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + [_c_float_p] * 13
                                   + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
@@ -378,6 +381,21 @@ class HipLib:
         out = torch.empty(K, 11, dtype=torch.float64, device=pred_theta.device)
         self._call("uglad_support_metrics", self._p(true_theta), self._p(pred_theta), ctypes.c_void_p(out.data_ptr()), K, D,
                    int(beta))
+        return out
+
+    def support_metrics_wide(self, true_theta, pred_theta, beta: int = 1):
+        """uglad_support_metrics_wide, every 2 <= D <= max_dim: two (K,D,D) fp32 tensors -> (K, 11) float64 tensor on the device.  The
+        edges of every pair are sorted by score on the device (csrc/metrics_wide.h); all but aupr is bit-equal to support_metrics."""
+        if true_theta.dim() != 3 or true_theta.shape != pred_theta.shape or true_theta.shape[1] != true_theta.shape[2]:
+            raise UgladError("support_metrics_wide: two tensors of shape (K, D, D)")
+        K, D, _ = pred_theta.shape
+        tp, pp = self._p(true_theta), self._p(pred_theta)
+        n = int(self._dll.uglad_support_metrics_wide_workspace_floats(int(K), int(D)))
+        if n < 0:
+            self._check("uglad_support_metrics_wide_workspace_floats", n)
+        wsp = torch.empty(n, dtype=torch.float32, device=pred_theta.device)  # must outlive the enqueue
+        out = torch.empty(K, 11, dtype=torch.float64, device=pred_theta.device)
+        self._call("uglad_support_metrics_wide", tp, pp, ctypes.c_void_p(out.data_ptr()), self._p(wsp), K, D, int(beta))
         return out
 
     def symeig(self, A, U, beta, jacobi: bool = False):

@@ -41,6 +41,7 @@ namespace uglad {
 #include "wide_ns.h"
 #include "cov_wide.h"
 #include "after_wide.h"
+#include "metrics_wide.h"
 #endif
 #include "theta0.h"
 #include "loss.h"

@@ -194,6 +194,31 @@ int uglad_support_metrics(const float* true_theta, const float* pred_theta, doub
   return launch_status();
 }
 
+int uglad_support_metrics_wide_workspace_floats(int K, int D) {
+  if (K < 1 || K > 65535 || D < 2 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  const size_t n = metrics_wide_layout(nullptr, D).total_floats(K);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+
+int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta, double* out, float* workspace, int K, int D, int beta,
+                               uglad_stream_t stream) {
+  if (!true_theta || !pred_theta || !out || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (uglad_support_metrics_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const MwView v = metrics_wide_layout(workspace, D).view;
+  const dim3 tiles(v.tiles, K), wg(kWThreads);
+  hipLaunchKernelGGL(mw_keys_kernel, dim3(v.nt, v.nt, K), wg, 0, st, true_theta, pred_theta, D, v);
+  for (int pass = 0; pass < kMwPasses; ++pass) {  // (an even number of passes: the sorted keys end in buffer 0)
+    hipLaunchKernelGGL(mw_hist_kernel, tiles, wg, 0, st, pass, pass & 1, v);
+    hipLaunchKernelGGL(mw_scan_kernel, dim3(K), wg, 0, st, v);
+    hipLaunchKernelGGL(mw_scatter_kernel, tiles, wg, 0, st, pass, pass & 1, v);
+  }
+  hipLaunchKernelGGL(mw_chunk_kernel, tiles, wg, 0, st, v);
+  hipLaunchKernelGGL(mw_group_kernel, tiles, wg, 0, st, v);
+  hipLaunchKernelGGL(mw_finish_kernel, dim3(K), wg, 0, st, out, beta, v);
+  return launch_status();
+}
+
 int uglad_tridiagonalize(const float* A0, const float* A1, const float* lam, float* R, float* workspace, int M, int D,
                          uglad_stream_t stream) {
   if (!A0 || !R || !workspace || (A1 && !lam)) return UGLAD_E_NULL;

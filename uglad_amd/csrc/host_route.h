@@ -281,3 +281,19 @@ static AfterWideLayout after_wide_layout(float* workspace, int D) {
   l.view = AfterwView{CovwView{reinterpret_cast<double*>(workspace), l.problem, l.DP}};
   return l;
 }
+
+// ---- workspace of the wide support-recovery metrics (metrics_wide.h, MwView), per pair, in 4-byte words (8-byte aligned; every part even):
+//   keys 0 | keys 1   E = D (D - 1) / 2 words each, rounded up to even: the two buffers of the radix sort
+//   hist   16 x tiles   digit counts / offsets of the pass (tiles = E over kMwTile, rounded up)
+//   kpart  nt x nt x 4  the counts of the key kernel's tiles (nt = D over 64, rounded up)
+//   chunk  tiles x 4 | mw2   tiles int64 | ap   tiles fp64   the group statistics' records and partial sums
+struct MetricsWideLayout {
+  MwView view;
+  size_t total_floats(int K) const { return (size_t)K * view.pair; }
+};
+static MetricsWideLayout metrics_wide_layout(float* workspace, int D) {
+  MetricsWideLayout l{};
+  const int E = D * (D - 1) / 2, tiles = (E + kMwTile - 1) / kMwTile, nt = (D + kMwKeyTile - 1) / kMwKeyTile;
+  l.view = MwView{reinterpret_cast<unsigned*>(workspace), mw_pair_words((size_t)E, (size_t)tiles, (size_t)nt), E, tiles, nt};
+  return l;
+}

@@ -733,9 +733,17 @@ class uGLAD_multitask(object):
 METRIC_KEYS = ("FDR", "TPR", "FPR", "SHD", "nnzTrue", "nnzPred", "precision", "recall", "Fbeta", "aupr", "auc")
 
 
+# Smallest D > max_eig_dim whose metrics report goes to uglad_support_metrics_wide; below it (and above max_eig_dim) the host formulation
+# would run.  0: the whole range goes to the device.  scripts/metrics_wide_probe.py times both sides; a range where the host wins end to
+# end belongs here.
+WIDE_METRICS_MIN_DIM = 0
+
+
 def device_report_metrics(true_theta, pred_theta, beta: int = 1):
     """`report_metrics_all` (ref utils/metrics.py:25-108) for K (true, predicted) precision matrices at once, counted on the
-    device (uglad_support_metrics): list of K dicts with the reference's keys, rounded to 3 decimals as the reference does."""
+    device: list of K dicts with the reference's keys, rounded to 3 decimals as the reference does.  D <= max_eig_dim:
+    uglad_support_metrics (one workgroup per pair); beyond, up to max_dim: uglad_support_metrics_wide (the edges sorted by score, many
+    workgroups per pair)."""
     lib = _lib.get_lib()
     dev = _lib.device()
     T = torch.as_tensor(np.asarray(true_theta.detach().cpu() if torch.is_tensor(true_theta) else true_theta).real,
@@ -745,13 +753,15 @@ def device_report_metrics(true_theta, pred_theta, beta: int = 1):
     G = G.detach().to(device=dev, dtype=torch.float32)
     if T.dim() == 2:
         T, G = T[None], G[None]
-    if T.shape[-1] > lib.max_eig_dim:
-        # beyond the counting kernel's size (one workgroup sweeps all D (D - 1) / 2 scores per true edge): the report is evaluated where the
-        # reference evaluates it -- on the host, from the same definitions (utils/metrics.py = ref utils/metrics.py:25-108).  After the path, once
-        # per fit; round 3 raised UgladError here AFTER all epochs of a fit(X, true_theta=...) at D > 256 had run.
+    D = T.shape[-1]
+    if D > lib.max_dim or lib.max_eig_dim < D < WIDE_METRICS_MIN_DIM:
+        # beyond what the device covers: the report is evaluated where the reference evaluates it -- on the host, from the same definitions
+        # (utils/metrics.py = ref utils/metrics.py:25-108).  After the path, once per fit; round 3 raised UgladError here AFTER all epochs
+        # of a fit(X, true_theta=...) at D > 256 had run.
         Tn, Gn = T.cpu().numpy(), G.cpu().numpy()
         return [report_metrics_all(Tn[k], Gn[k], beta=beta) for k in range(Tn.shape[0])]
-    out = lib.support_metrics(T.contiguous(), G.contiguous(), beta=beta).cpu().numpy()
+    metrics = lib.support_metrics if D <= lib.max_eig_dim else lib.support_metrics_wide
+    out = metrics(T.contiguous(), G.contiguous(), beta=beta).cpu().numpy()
     return [{k: round(float(v), 3) for k, v in zip(METRIC_KEYS, row)} for row in out]
 
 
