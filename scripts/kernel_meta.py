@@ -5,13 +5,15 @@ uglad_amd/csrc/libuglad_hip.so with the ROCm LLVM tools; nothing is run on a GPU
 
     python scripts/kernel_meta.py [--so PATH] [--filter SUBSTR] [--loops] > profiles/rNN_kernel_meta.txt
         (--loops disassembles every kernel of the table: about a minute for the whole library, seconds with --filter)
-    python scripts/kernel_meta.py [--so PATH] --diff OTHER.so
+    python scripts/kernel_meta.py [--so PATH] --diff OTHER.so [--alias OLD=NEW ...]
 
 --loops disassembles every kernel and counts scratch_load / scratch_store instructions inside backward-branch spans, the global load
 instructions (gld) and the s_waitcnt with vmcnt <= 1 (vmwait): a kernel that waits about as often as it loads fetches its data one round
 trip at a time (an `inside ? load : 0` that became a branch per entry, a load whose register another load's address was allocated into).
 --diff compares the two libraries function by function (kernels and the device functions they call): the resource figures of the table and
 the instruction encodings of the disassembly, addresses left out.  Exit status 1 on any difference -- what a refactor has to leave at 0.
+--alias OLD=NEW (repeatable; exact symbols, as the "only in" lines print them): a function the refactor renamed -- OTHER.so's OLD is compared
+with --so's NEW.
 """
 from __future__ import annotations
 
@@ -149,10 +151,16 @@ def functions(so: str, td: str):
     return meta, code
 
 
-def diff(so_a: str, so_b: str) -> int:
+def diff(so_a: str, so_b: str, aliases=()) -> int:
     with tempfile.TemporaryDirectory() as td:
         meta_a, code_a = functions(so_a, os.path.join(td, "a"))
         meta_b, code_b = functions(so_b, os.path.join(td, "b"))
+    for old, new in (a.split("=", 1) for a in aliases):  # so_b's OLD goes by so_a's name NEW
+        if old not in code_b or new not in code_a:
+            raise SystemExit(f"--alias {old}={new}: {old} is not in {so_b} or {new} is not in {so_a}")
+        code_b[new] = [(enc.replace(old, new), text) for enc, text in code_b.pop(old)]  # (a branch prints its target as <function+offset>)
+        if old in meta_b:
+            meta_b[new] = meta_b.pop(old)
     bad = 0
     for sym in sorted(set(code_a) ^ set(code_b)):
         print(f"only in {so_a if sym in code_a else so_b}: {sym}")
@@ -184,9 +192,10 @@ def main():
     ap.add_argument("--filter", default="")
     ap.add_argument("--loops", action="store_true")
     ap.add_argument("--diff", metavar="OTHER.so", help="compare --so with this library instead of printing the table")
+    ap.add_argument("--alias", metavar="OLD=NEW", action="append", default=[], help="with --diff: OTHER.so's function OLD is --so's NEW")
     a = ap.parse_args()
     if a.diff:
-        return diff(a.so, a.diff)
+        return diff(a.so, a.diff, a.alias)
     with tempfile.TemporaryDirectory() as td:
         cos = extract_code_object(a.so, td)
         if isinstance(cos, str):

@@ -177,6 +177,24 @@ def test_emulated_argument_errors_and_nan_column(emul):
     assert np.isfinite(S[0][ok]).all() and relerr(S[0][ok], ref[0][ok]) < TOL
 
 
+def test_emulated_wide_workspace_sizes_are_the_recorded_ones(emul):
+    """The ABI-visible sizes and error codes of the three wide utilities (covariance, conditional mean, support metrics) against
+    tests/golden/wide_workspace_floats.json.  The fixture was recorded at the parent commit of the one that moved the layouts into the kernel
+    headers' view factories, from that build's own `*_workspace_floats`: per entry point K in {1, 3} x D in {1, 2, 63, 64, 65, 288, 2048}
+    and the four refusals K = 0, K = 65536, D = 0, D = 2049 (for the metrics D = 1 is a refusal too), 18 rows each."""
+    import json
+
+    with open(os.path.join(GOLDEN, "wide_workspace_floats.json")) as f:
+        recorded = json.load(f)
+    names = [k for k in recorded if k.startswith("uglad_")]
+    assert len(names) == 3
+    for name in names:
+        fn = getattr(emul._dll, name)
+        assert len(recorded[name]) == 18
+        for K, D, expected in recorded[name]:
+            assert int(fn(K, D)) == expected, (name, K, D)
+
+
 # ============================================================================================ GPU
 WIDE = ["widecov_k2_n40_d288_singular", "widecov_k1_n97_d320", "widecov_k1_n400_d300_rank250"]
 

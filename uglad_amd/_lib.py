@@ -118,6 +118,24 @@ class HipLib:
             raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
         return ctypes.c_void_p(t.data_ptr())
 
+    @staticmethod
+    def _vp(t: Optional[torch.Tensor]):
+        """Pointer of a tensor that is not fp32 (fp64 tables, results); its dtype and placement are the caller's to check."""
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def _require_f64(self, t: torch.Tensor, ndim: int, what: str) -> None:
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != ndim:
+            raise UgladError(what)
+        if self.require_gpu and not t.is_cuda:
+            raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
+
+    def _wide_workspace(self, name: str, K: int, D: int, device) -> torch.Tensor:
+        """Scratch of <name>_workspace_floats(K, D) floats for one call of the wide entry point `name`; must outlive the enqueue."""
+        n = int(getattr(self._dll, name + "_workspace_floats")(int(K), int(D)))
+        if n < 0:
+            self._check(name + "_workspace_floats", n)
+        return torch.empty(n, dtype=torch.float32, device=device)
+
     def _stream(self):
         if not self.require_gpu:
             return None
@@ -314,21 +332,15 @@ class HipLib:
         """(K,N,D) FLOAT64 tables on the device -> (K,D,D) fp32 covariances for every D <= max_dim (uglad_covariance_wide): fp64
         throughout, the repair decided by a Cholesky bisection instead of an eigensolver.  With `return_min_eig` also the (K,) fp64
         smallest eigenvalues before the repair (+inf for a table that needed none) and the (K,) bool mask of the repaired tables."""
-        if X64.dtype != torch.float64 or not X64.is_contiguous() or X64.dim() != 3:
-            raise UgladError("covariance_wide takes a contiguous (K, N, D) float64 tensor")
-        if self.require_gpu and not X64.is_cuda:
-            raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
+        self._require_f64(X64, 3, "covariance_wide takes a contiguous (K, N, D) float64 tensor")
         if return_min_eig and not repair:
             raise UgladError("return_min_eig needs repair=True (the eigenvalue comes from the repair's bisection)")
         K, N, D = X64.shape
-        n = int(self._dll.uglad_covariance_wide_workspace_floats(int(K), int(D)))
-        if n < 0:
-            self._check("uglad_covariance_wide_workspace_floats", n)
-        wsp = torch.empty(n, dtype=torch.float32, device=X64.device)  # must outlive the enqueue
+        wsp = self._wide_workspace("uglad_covariance_wide", K, D, X64.device)
         S = torch.empty(K, D, D, dtype=torch.float32, device=X64.device)
         mn = torch.empty(K, dtype=torch.float64, device=X64.device) if repair else None
-        self._call("uglad_covariance_wide", ctypes.c_void_p(X64.data_ptr()), K, N, D, int(bool(normalize)), float(eval_offset),
-                   self._p(S), ctypes.c_void_p(mn.data_ptr()) if repair else None, self._p(wsp))
+        self._call("uglad_covariance_wide", self._vp(X64), K, N, D, int(bool(normalize)), float(eval_offset), self._p(S), self._vp(mn),
+                   self._p(wsp))
         if return_min_eig:
             return S, mn, ~torch.isinf(mn)
         return S
@@ -348,25 +360,18 @@ class HipLib:
         """uglad_conditional_mean_wide, every D <= max_dim: (K,D,D), (K,D) FLOAT64, (K,D) fp32 mask, (K,D) FLOAT64 -> full_mean (K,D)
         float64, cond_cov (K,D,D) fp32 (None without `want_cov`: the product is skipped), log_pdf (K) float64.  A problem whose L_uu is
         not positive definite comes back with NaN in log_pdf, in the unobserved entries of full_mean and in the (u, u) block of cond_cov."""
-        for a, shape in ((P64, 3), (mean64, 2), (values64, 2)):
-            if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() != shape:
-                raise UgladError("conditional_mean_wide takes contiguous float64 tensors (K, D, D), (K, D), (K, D) and a float32 mask")
-            if self.require_gpu and not a.is_cuda:
-                raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
+        for a, ndim in ((P64, 3), (mean64, 2), (values64, 2)):
+            self._require_f64(a, ndim, "conditional_mean_wide takes contiguous float64 tensors (K, D, D), (K, D), (K, D) and a float32 mask")
         K, D, _ = P64.shape
         if P64.shape[2] != D or tuple(mean64.shape) != (K, D) or tuple(values64.shape) != (K, D) or tuple(observed.shape) != (K, D):
             raise UgladError("conditional_mean_wide: shapes (K, D, D), (K, D), (K, D), (K, D)")
-        n = int(self._dll.uglad_conditional_mean_wide_workspace_floats(int(K), int(D)))
-        if n < 0:
-            self._check("uglad_conditional_mean_wide_workspace_floats", n)
         dev = P64.device
-        wsp = torch.empty(n, dtype=torch.float32, device=dev)  # must outlive the enqueue
+        wsp = self._wide_workspace("uglad_conditional_mean_wide", K, D, dev)
         full_mean = torch.empty(K, D, dtype=torch.float64, device=dev)
         log_pdf = torch.empty(K, dtype=torch.float64, device=dev)
         cond_cov = torch.empty(K, D, D, dtype=torch.float32, device=dev) if want_cov else None
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        self._call("uglad_conditional_mean_wide", vp(P64), vp(mean64), self._p(observed), vp(values64), vp(full_mean), self._p(cond_cov),
-                   vp(log_pdf), self._p(wsp), K, D, int(bool(clip01)))
+        self._call("uglad_conditional_mean_wide", self._vp(P64), self._vp(mean64), self._p(observed), self._vp(values64), self._vp(full_mean),
+                   self._p(cond_cov), self._vp(log_pdf), self._p(wsp), K, D, int(bool(clip01)))
         return full_mean, cond_cov, log_pdf
 
     def partial_correlations(self, precision):
@@ -390,12 +395,9 @@ class HipLib:
             raise UgladError("support_metrics_wide: two tensors of shape (K, D, D)")
         K, D, _ = pred_theta.shape
         tp, pp = self._p(true_theta), self._p(pred_theta)
-        n = int(self._dll.uglad_support_metrics_wide_workspace_floats(int(K), int(D)))
-        if n < 0:
-            self._check("uglad_support_metrics_wide_workspace_floats", n)
-        wsp = torch.empty(n, dtype=torch.float32, device=pred_theta.device)  # must outlive the enqueue
+        wsp = self._wide_workspace("uglad_support_metrics_wide", K, D, pred_theta.device)
         out = torch.empty(K, 11, dtype=torch.float64, device=pred_theta.device)
-        self._call("uglad_support_metrics_wide", tp, pp, ctypes.c_void_p(out.data_ptr()), self._p(wsp), K, D, int(beta))
+        self._call("uglad_support_metrics_wide", tp, pp, self._vp(out), self._p(wsp), K, D, int(beta))
         return out
 
     def symeig(self, A, U, beta, jacobi: bool = False):

@@ -1,5 +1,5 @@
 // After the path beyond the eigensolver's size (uglad_conditional_mean_wide: every D up to the cell's own limit), fp64 throughout: the
-// conditional Gaussian / MAP estimate given observed coordinates (main.py:1176-1260) as a second client of cov_wide.h's tile product and
+// conditional Gaussian / MAP estimate given observed coordinates (main.py:1176-1260) as a second client of chol_wide.h's tile layer and
 // blocked Cholesky.  after_path.h's map_solve_kernel inverts the masked matrix with the one-workgroup eigensolver and stops at D = 256;
 // L_uu is symmetric positive definite in every legitimate call, so a Cholesky factorisation gives solve, inverse and log-determinant.
 //
@@ -10,11 +10,9 @@
 //                           of r_u = sum_{j observed} P_uj (x_j - mean_j), columns over waves combined in wave order
 //   afterw_rhs_kernel       r = the parts summed over the block columns in order (0 on observed coordinates and in the padding); the control
 //                           block of the factorisation (sigma = 0, active, not flagged)
-//   covw_chol_update_kernel, covw_chol_panel_kernel<true>
-//                           A = L L^T, two launches per block column (cov_wide.h).  The diagonal tile's workgroup also forms L(j, j)^-T -- the
-//                           panel's own solve, applied to the identity -- and the 64 log-pivots, and writes them to slabs of their own (never
-//                           over tile (j, j) of L, which the other workgroups of that launch are still reading).  A pivot that is <= 0 or NaN
-//                           raises the problem's flag; every later gated launch returns at once for it
+//   cholw_update_kernel, cholw_panel_kernel<CholwInvView>
+//                           A = L L^T, two launches per block column, which also leave L(j, j)^-T and the log-pivots (chol_wide.h).  A pivot
+//                           that is <= 0 or NaN raises the problem's flag; every later gated launch returns at once for it
 //   afterw_subst_kernel     W = L^-1 by block forward substitution, one launch per block row i: W(i, j) = -L(i, i)^-1 sum_{j <= p < i} L(i, p) W(p, j)
 //                           for all j < i, a tile product and a 64 x 64 triangular multiply.  W is kept TRANSPOSED (Wt = L^-T, block upper
 //                           triangular): then both operands of every tile product here and in afterw_cov_kernel run along k, like rows of L
@@ -34,23 +32,36 @@
 // Every sum has a fixed order, so results are bit-reproducible and independent of the batch.  Nothing reads back to the host: the sequence
 // (2 + 2 nt + (nt - 1) + 5 + 1 + 1 launches, nt = DP / 64) is one linear chain and can be captured into a graph.
 #pragma once
-#include "cov_wide.h"
+#include "chol_wide.h"
 
 namespace uglad {
 
-// what the kernels take: the factorisation's view (A = s64, L = w, the vectors r | y | t in the statistics' place, the control block, Wt and
-// the log-pivots behind it) and, behind those, one more vector and the parts of r (host_route.h, AfterWideLayout)
+// A problem's part of the workspace, in DOUBLES (the buffer is 8-byte aligned; DP = D rounded up to 64): the factorisation's slab with the
+// inverse (CholwInvView) --
+//   A     DP x DP   the masked precision matrix, identity on the observed coordinates and in the padding
+//   L     DP x DP   its Cholesky factor: the tiles below the block diagonal
+//   r | y | t   3 DP   right-hand side, solution, intermediate
+//   CholwCtl   8   only the "not PD" flag is live (sigma = 0, always active)
+//   Wt    DP x DP   L^-T, block upper triangular
+//   log pivots   DP
+// -- and behind it
+//   residual   DP   the fourth vector
+//   parts of r   DP / 64 x DP   one row per block column of A
 struct AfterwView {
-  CovwView c;
+  CholwInvView c;
   enum Vec { kR = 0, kY = 1, kT = 2, kRes = 3 };
-  __host__ __device__ double* vec(int t, int which) const {
-    return which < 3 ? c.stats(t) + (size_t)which * c.DP : c.log_pivot(t) + c.DP;
-  }
+  __host__ __device__ double* vec(int t, int which) const { return which < 3 ? c.vec3(t) + (size_t)which * c.DP : c.log_pivot(t) + c.DP; }
   __host__ __device__ double* rparts(int t) const { return c.log_pivot(t) + 2 * (size_t)c.DP; }  // [DP / 64][DP]
 };
 __host__ __device__ constexpr size_t afterw_problem_doubles(int DP) {
-  return covw_table_doubles(DP) + (size_t)DP * DP + 2 * (size_t)DP + (size_t)(DP / kCovwT) * DP;
+  return cholw_slab_doubles(DP) + (size_t)DP * DP + 2 * (size_t)DP + (size_t)(DP / kT64) * DP;
 }
+// (the friend that chol_wide.h's CholwInvView names: the one place that view is made)
+__host__ inline AfterwView afterw_view(float* workspace, int D) {
+  const int DP = t64_padded(D);
+  return AfterwView{CholwInvView(CholwView{reinterpret_cast<double*>(workspace), afterw_problem_doubles(DP), DP})};
+}
+__host__ inline size_t afterw_problem_floats(int D) { return 2 * afterw_problem_doubles(t64_padded(D)); }
 
 struct AfterwIn {
   const double* P;       // (K, D, D), the upper triangle is read
@@ -63,20 +74,17 @@ struct AfterwIn {
 // grid (DP / 64, DP / 64, K): tile (I, J) = (blockIdx.y, blockIdx.x).  The tile (min, max) of P goes through LDS, so the lower tiles are
 // the transposes of the upper ones to the bit.
 __global__ __launch_bounds__(kWThreads) void afterw_prepare_kernel(AfterwIn in, int D, AfterwView v) {
-  __shared__ double s_p[kCovwT * kCovwLdt], s_d[kCovwT], s_part[4][kCovwT];
-  __shared__ int s_ob[2][kCovwT];
+  __shared__ double s_p[kT64 * kT64Ldt], s_d[kT64], s_part[4][kT64];
+  __shared__ int s_ob[2][kT64];
   const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z, DP = v.c.DP;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool upper = I <= J;
-  const int a0 = (upper ? I : J) * kCovwT, b0 = (upper ? J : I) * kCovwT;  // the tile of P that is read
+  const int a0 = (upper ? I : J) * kT64, b0 = (upper ? J : I) * kT64;  // the tile of P that is read
   const double* Pt = in.P + (size_t)t * D * D;
   const float* ob = in.observed + (size_t)t * D;
-  for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) {
-    const int a = idx >> 6, b = idx & 63;
-    s_p[a * kCovwLdt + b] = (a0 + a < D && b0 + b < D) ? Pt[(size_t)(a0 + a) * D + b0 + b] : 0.0;
-  }
-  if (tid < kCovwT) {
-    const int i = I * kCovwT + tid, j = J * kCovwT + tid;
+  t64_for_each_element([&](int a, int b) { s_p[a * kT64Ldt + b] = (a0 + a < D && b0 + b < D) ? Pt[(size_t)(a0 + a) * D + b0 + b] : 0.0; });
+  if (tid < kT64) {
+    const int i = I * kT64 + tid, j = J * kT64 + tid;
     s_ob[0][tid] = i >= D || ob[i] != 0.f;  // (the padding counts as observed: identity, no part in r)
     const bool obj = j < D && ob[j] != 0.f;
     s_ob[1][tid] = j >= D || obj;
@@ -85,38 +93,33 @@ __global__ __launch_bounds__(kWThreads) void afterw_prepare_kernel(AfterwIn in, 
   __syncthreads();
   // element (x, y) of the symmetric matrix's tile (I, J): from the upper triangle
   auto el = [&](int x, int y) {
-    if (I == J) return x <= y ? s_p[x * kCovwLdt + y] : s_p[y * kCovwLdt + x];
-    return upper ? s_p[x * kCovwLdt + y] : s_p[y * kCovwLdt + x];
+    if (I == J) return x <= y ? s_p[x * kT64Ldt + y] : s_p[y * kT64Ldt + x];
+    return upper ? s_p[x * kT64Ldt + y] : s_p[y * kT64Ldt + x];
   };
-  double* A = v.c.s64(t);
-  for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) {
-    const int x = idx >> 6, y = idx & 63;
+  double* A = v.c.a(t);
+  t64_for_each_element([&](int x, int y) {
     const bool keep = !s_ob[0][x] && !s_ob[1][y];
-    A[(size_t)(I * kCovwT + x) * DP + J * kCovwT + y] = keep ? el(x, y) : ((I == J && x == y) ? 1.0 : 0.0);
-  }
+    A[(size_t)(I * kT64 + x) * DP + J * kT64 + y] = keep ? el(x, y) : ((I == J && x == y) ? 1.0 : 0.0);
+  });
   // r's part from this block column: row = lane, columns w, w + 4, ...; the four partial sums combined in wave order
   double part = 0.0;
-  for (int y = w; y < kCovwT; y += 4)
+  for (int y = w; y < kT64; y += 4)
     if (s_ob[1][y]) part = fma(el(lane, y), s_d[y], part);  // (s_d is 0 in the padding)
   s_part[w][lane] = part;
   __syncthreads();
-  if (w == 0) v.rparts(t)[(size_t)J * DP + I * kCovwT + lane] = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+  if (w == 0) v.rparts(t)[(size_t)J * DP + I * kT64 + lane] = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
 }
 
 // grid (DP / 64, K), 64 threads
 __global__ __launch_bounds__(64) void afterw_rhs_kernel(const float* __restrict__ observed, int D, AfterwView v) {
-  const int t = blockIdx.y, i = blockIdx.x * kCovwT + threadIdx.x, DP = v.c.DP;
+  const int t = blockIdx.y, i = blockIdx.x * kT64 + threadIdx.x, DP = v.c.DP;
   double r = 0.0;
   if (i < D && observed[(size_t)t * D + i] == 0.f) {
     const double* parts = v.rparts(t);
-    for (int J = 0; J < DP / kCovwT; ++J) r += parts[(size_t)J * DP + i];
+    for (int J = 0; J < DP / kT64; ++J) r += parts[(size_t)J * DP + i];
   }
   v.vec(t, AfterwView::kR)[i] = r;
-  if (i == 0) {
-    CovwCtl* ctl = v.c.ctl(t);
-    ctl->lo = ctl->hi = ctl->min_eig = ctl->sigma = 0.0;
-    ctl->notpd = 0, ctl->active = 1, ctl->repaired = 0, ctl->pad = 0;
-  }
+  if (i == 0) v.c.ctl(t)->reset(0.0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- W = L^-1, block row i
@@ -124,42 +127,28 @@ __global__ __launch_bounds__(64) void afterw_rhs_kernel(const float* __restrict_
 // M(x, q) T(q, y) with M = L(i, i)^-1, read from its transpose in tile (i, i) of Wt (written by the panel launch of block column i).
 // This launch writes block column i of Wt and reads block columns j .. i - 1 of it.
 __global__ __launch_bounds__(kWThreads) void afterw_subst_kernel(int i, AfterwView v) {
-  __shared__ __attribute__((aligned(16))) double s_stage[2 * kCovwStage];
-  __shared__ double s_m[kCovwT * kCovwLdt];
+  __shared__ __attribute__((aligned(16))) double s_stage[2 * kT64Stage];
+  __shared__ double s_m[kT64 * kT64Ldt];
   const int t = blockIdx.y;
-  if (!covw_gate(v.c.ctl(t))) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, DP = v.c.DP;
-  const int j = blockIdx.x, i0 = i * kCovwT, j0 = j * kCovwT;
-  const double* L = v.c.w(t);
+  if (!cholw_gate(v.c.ctl(t))) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, DP = v.c.DP;
+  const int j = blockIdx.x, i0 = i * kT64, j0 = j * kT64;
+  const double* L = v.c.l(t);
   double* Wt = v.c.inv_t(t);
   const double* rows[2] = {L + (size_t)i0 * DP, Wt + (size_t)j0 * DP};
   f64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[a][c] = (f64x4){0.0, 0.0, 0.0, 0.0};
-  covw_tile_product<true>(j0, i0, [&](int which, int x, int k) { return rows[which][(size_t)x * DP + k]; }, s_stage, s_stage + kCovwStage, acc);
-  for (int idx = tid; idx < kCovwT * kCovwT; idx += kWThreads) {  // s_m[x][q] = M(x, q) = Wt(i0 + q, i0 + x)
-    const int q = idx >> 6, x = idx & 63;
-    s_m[x * kCovwLdt + q] = Wt[(size_t)(i0 + q) * DP + i0 + x];
-  }
-  __syncthreads();  // (the last chunk has been consumed: the staging area becomes T, [q][y] with row stride kCovwLdt)
+  t64_zero(acc);
+  t64_tile_product<true>(j0, i0, [&](int which, int x, int k) { return rows[which][(size_t)x * DP + k]; }, s_stage, s_stage + kT64Stage, acc);
+  t64_for_each_element([&](int q, int x) { s_m[x * kT64Ldt + q] = Wt[(size_t)(i0 + q) * DP + i0 + x]; });  // s_m[x][q] = M(x, q) = Wt(i0 + q, i0 + x)
+  __syncthreads();  // (the last chunk has been consumed: the staging area becomes T, [q][y] with row stride kT64Ldt)
   double* s_tt = s_stage;
-  static_assert(kCovwT * kCovwLdt <= 2 * kCovwStage, "T fits the staging area");
-  {
-    const int l16 = lane & 15, kq = lane >> 4, ri = (w >> 1) * 32, rj = (w & 1) * 32;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_tt[(ri + 16 * a + kq + 4 * r) * kCovwLdt + rj + 16 * c + l16] = acc[a][c][r];
-  }
+  static_assert(kT64 * kT64Ldt <= 2 * kT64Stage, "T fits the staging area");
+  t64_for_each_fragment([&](int a, int c, int r, int row, int col) { s_tt[row * kT64Ldt + col] = acc[a][c][r]; });
   __syncthreads();
   // thread = row x (lane) x columns y = w, w + 4, ...: the stores run along x, a row of Wt
-  for (int y = w; y < kCovwT; y += 4) {
+  for (int y = w; y < kT64; y += 4) {
     double s = 0.0;
-    for (int q = 0; q <= lane; ++q) s = fma(s_m[lane * kCovwLdt + q], s_tt[q * kCovwLdt + y], s);
+    for (int q = 0; q <= lane; ++q) s = fma(s_m[lane * kT64Ldt + q], s_tt[q * kT64Ldt + y], s);
     Wt[(size_t)(j0 + y) * DP + i0 + lane] = -s;
   }
 }
@@ -172,16 +161,16 @@ __global__ __launch_bounds__(kWThreads) void afterw_subst_kernel(int i, AfterwVi
 enum { kAfterwLower = 0, kAfterwUpper = 1, kAfterwResidual = 2 };
 template <bool kRows>
 __global__ __launch_bounds__(kWThreads) void afterw_matvec_kernel(int which, int src, int dst, int accumulate, AfterwView v) {
-  __shared__ double s_part[4][kCovwT];
+  __shared__ double s_part[4][kT64];
   const int t = blockIdx.y;
-  if (!covw_gate(v.c.ctl(t))) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, DP = v.c.DP, i0 = blockIdx.x * kCovwT;
-  const double* Mx = which == kAfterwResidual ? v.c.s64(t) : v.c.inv_t(t);
+  if (!cholw_gate(v.c.ctl(t))) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, DP = v.c.DP, i0 = blockIdx.x * kT64;
+  const double* Mx = which == kAfterwResidual ? v.c.a(t) : v.c.inv_t(t);
   const double* x = v.vec(t, src);
   double* out = v.vec(t, dst);
-  const int k0 = which == kAfterwUpper ? i0 : 0, k1 = which == kAfterwLower ? i0 + kCovwT : DP;
+  const int k0 = which == kAfterwUpper ? i0 : 0, k1 = which == kAfterwLower ? i0 + kT64 : DP;
   if constexpr (kRows) {
-    for (int o = w; o < kCovwT; o += 4) {
+    for (int o = w; o < kT64; o += 4) {
       const double* row = Mx + (size_t)(i0 + o) * DP;
       double s = 0.0;
       for (int k = k0 + lane; k < k1; k += 64) s = fma(row[k], x[k], s);
@@ -213,38 +202,26 @@ __global__ __launch_bounds__(kWThreads) void afterw_matvec_kernel(int which, int
 // grid (DP / 64, DP / 64, K); tiles below the diagonal return.  X(I, J) = sum_{k >= 64 J} Wt(I0 + x, k) Wt(J0 + y, k).  Not gated: a flagged
 // problem gets NaN on its (u, u) block.
 __global__ __launch_bounds__(kWThreads) void afterw_cov_kernel(const float* __restrict__ observed, int D, AfterwView v, float* __restrict__ cond_cov) {
-  __shared__ __attribute__((aligned(16))) double s_stage[2 * kCovwStage];
+  __shared__ __attribute__((aligned(16))) double s_stage[2 * kT64Stage];
   const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z;
   if (I > J) return;  // (uniform per workgroup)
-  const bool ok = covw_gate(v.c.ctl(t));
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, DP = v.c.DP;
+  const bool ok = cholw_gate(v.c.ctl(t));
+  const int DP = v.c.DP;
   const double* Wt = v.c.inv_t(t);
-  const double* rows[2] = {Wt + (size_t)I * kCovwT * DP, Wt + (size_t)J * kCovwT * DP};
+  const double* rows[2] = {Wt + (size_t)I * kT64 * DP, Wt + (size_t)J * kT64 * DP};
   f64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[a][c] = (f64x4){0.0, 0.0, 0.0, 0.0};
+  t64_zero(acc);
   if (ok)
-    covw_tile_product<true>(J * kCovwT, DP, [&](int which, int x, int k) { return rows[which][(size_t)x * DP + k]; }, s_stage, s_stage + kCovwStage, acc);
-  const int l16 = lane & 15, kq = lane >> 4, ri = (w >> 1) * 32, rj = (w & 1) * 32;
+    t64_tile_product<true>(J * kT64, DP, [&](int which, int x, int k) { return rows[which][(size_t)x * DP + k]; }, s_stage, s_stage + kT64Stage, acc);
   const float* ob = observed + (size_t)t * D;
   float* C = cond_cov + (size_t)t * D * D;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int j = J * kCovwT + rj + 16 * c + l16;
-      const bool obj = j < D && ob[j] != 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = I * kCovwT + ri + 16 * a + kq + 4 * r;
-        if (i > j || j >= D) continue;  // (the diagonal tile: its lower half is the mirror of its upper half)
-        const float val = (obj || ob[i] != 0.f) ? (i == j ? 1.f : 0.f) : (ok ? (float)acc[a][c][r] : __builtin_nanf(""));
-        C[(size_t)i * D + j] = val;
-        if (i != j) C[(size_t)j * D + i] = val;
-      }
-    }
+  t64_for_each_fragment([&](int a, int c, int r, int row, int col) {
+    const int i = I * kT64 + row, j = J * kT64 + col;
+    if (i > j || j >= D) return;  // (the diagonal tile: its lower half is the mirror of its upper half)
+    const float val = (ob[j] != 0.f || ob[i] != 0.f) ? (i == j ? 1.f : 0.f) : (ok ? (float)acc[a][c][r] : __builtin_nanf(""));
+    C[(size_t)i * D + j] = val;
+    if (i != j) C[(size_t)j * D + i] = val;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- full_mean and log_pdf
@@ -254,10 +231,10 @@ __global__ __launch_bounds__(kWThreads) void afterw_finish_kernel(AfterwIn in, i
   __shared__ double s_sum[kWThreads];
   __shared__ int s_nu[kWThreads];
   const int t = blockIdx.y, tid = threadIdx.x, DP = v.c.DP;
-  const bool ok = covw_gate(v.c.ctl(t));
+  const bool ok = cholw_gate(v.c.ctl(t));
   const float* ob = in.observed + (size_t)t * D;
-  const int i = blockIdx.x * kCovwT + tid;
-  if (tid < kCovwT && i < D) {
+  const int i = blockIdx.x * kT64 + tid;
+  if (tid < kT64 && i < D) {
     double val;
     if (ob[i] != 0.f) val = in.values[(size_t)t * D + i];
     else val = ok ? in.mean[(size_t)t * D + i] - v.vec(t, AfterwView::kY)[i] : __builtin_nan("");

@@ -4,6 +4,25 @@
 // the route of a utility: its batch is one group, and only the tridiagonalisation flavour is asked of it
 static Route util_route(int M, int D) { return make_route(M, D, 1, false, UGLAD_SQRT_EXACT); }
 
+// ---- the many-workgroup fp64 utilities (chol_wide.h and its clients, metrics_wide.h).  Their workspaces are described once, by the view in the
+// kernel header and its factory; here are the checks and the launches they share.
+// *_workspace_floats: K items of floats_per_item(D) floats, for min_D <= D <= UGLAD_MAX_DIM; a size beyond 2^31 - 1 is refused like a dimension
+static int wide_workspace_floats(int K, int D, int min_D, size_t (*floats_per_item)(int D)) {
+  if (K < 1 || K > 65535 || D < min_D || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  const size_t n = (size_t)K * floats_per_item(D);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+static bool wide_workspace_ok(const float* workspace) { return workspace && !(reinterpret_cast<size_t>(workspace) & 7); }
+// the blocked Cholesky of K slabs: update + panel for every block column; a CholwInvView also gets L(j, j)^-T and the log-pivots
+template <class View>
+static void launch_cholw(hipStream_t st, int K, const View& v) {
+  const int nt = v.DP / kT64;
+  for (int j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(cholw_update_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, static_cast<const CholwView&>(v));
+    hipLaunchKernelGGL(cholw_panel_kernel<View>, dim3(nt - j, K), dim3(kWThreads), 0, st, j, v);
+  }
+}
+
 extern "C" {
 
 int uglad_consensus_partial(const float* theta_K, int K, int D, float* absmin, float* signsum, uglad_stream_t stream) {
@@ -54,36 +73,28 @@ int uglad_covariance(const float* X, int K, int N, int D, int normalize, float e
   return launch_status();
 }
 
-int uglad_covariance_wide_workspace_floats(int K, int D) {
-  if (K < 1 || K > 65535 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const size_t n = cov_wide_layout(nullptr, D).total_floats(K);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
+int uglad_covariance_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, covw_table_floats); }
 
 int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, double eval_offset, float* S_out, double* min_eig_out,
                           float* workspace, uglad_stream_t stream) {
-  if (!X || !S_out || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (!X || !S_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
   if (uglad_covariance_wide_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
   if (normalize != 0 && normalize != 1) return UGLAD_E_MODE;
   hipStream_t st = (hipStream_t)stream;
-  const CovWideLayout l = cov_wide_layout(workspace, D);
-  const int nt = l.DP / kCovwT;
-  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X, N, D, normalize, l.view);
-  hipLaunchKernelGGL(covw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, l.view, S_out);
+  const CholwView v = covw_view(workspace, D);
+  const int nt = v.DP / kT64;
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X, N, D, normalize, v);
+  hipLaunchKernelGGL(covw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, v, S_out);
   if (!min_eig_out) return launch_status();  // no repair
   // the test at the threshold, then the bisection: tables that are done (or whose factorisation has broken down) cost empty launches
   for (int step = 0; step <= kCovwSteps; ++step) {
-    hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, l.view);
-    for (int j = 0; j < nt; ++j) {
-      hipLaunchKernelGGL(covw_chol_update_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
-      hipLaunchKernelGGL(covw_chol_panel_kernel<false>, dim3(nt - j, K), dim3(kWThreads), 0, st, j, l.view);
-    }
+    hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, v);
+    launch_cholw(st, K, v);
   }
-  hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, kCovwSteps, D, l.view);
-  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, l.view, S_out, min_eig_out);
+  hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, kCovwSteps, D, v);
+  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, v, S_out, min_eig_out);
   return launch_status();
 }
-
 
 #ifdef UGLAD_PHASE_EXIT
 int uglad_diag_set_exit(int at) {  // (development build: see glad_device.h)
@@ -137,29 +148,21 @@ int uglad_conditional_mean(const float* precision, const float* mean, const floa
   return launch_status();
 }
 
-int uglad_conditional_mean_wide_workspace_floats(int K, int D) {
-  if (K < 1 || K > 65535 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const size_t n = after_wide_layout(nullptr, D).total_floats(K);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
+int uglad_conditional_mean_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, afterw_problem_floats); }
 
 int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,
                                 double* full_mean, float* cond_cov, double* log_pdf, float* workspace, int K, int D, int clip01,
                                 uglad_stream_t stream) {
-  if (!precision || !mean || !observed || !values || !full_mean || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (!precision || !mean || !observed || !values || !full_mean || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
   if (uglad_conditional_mean_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
   hipStream_t st = (hipStream_t)stream;
-  const AfterWideLayout l = after_wide_layout(workspace, D);
-  const AfterwView v = l.view;
+  const AfterwView v = afterw_view(workspace, D);
   const AfterwIn in{precision, mean, observed, values};
-  const int nt = l.DP / kCovwT;
+  const int nt = v.c.DP / kT64;
   const dim3 rows(nt, K), tiles(nt, nt, K), wg(kWThreads);
   hipLaunchKernelGGL(afterw_prepare_kernel, tiles, wg, 0, st, in, D, v);
   hipLaunchKernelGGL(afterw_rhs_kernel, rows, dim3(64), 0, st, observed, D, v);
-  for (int j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(covw_chol_update_kernel, dim3(nt - j, K), wg, 0, st, j, v.c);
-    hipLaunchKernelGGL(covw_chol_panel_kernel<true>, dim3(nt - j, K), wg, 0, st, j, v.c);
-  }
+  launch_cholw(st, K, v.c);
   for (int i = 1; i < nt; ++i) hipLaunchKernelGGL(afterw_subst_kernel, dim3(i, K), wg, 0, st, i, v);
   // y = W^T (W r); y += W^T (W (r - A y))
   using V = AfterwView;
@@ -194,18 +197,14 @@ int uglad_support_metrics(const float* true_theta, const float* pred_theta, doub
   return launch_status();
 }
 
-int uglad_support_metrics_wide_workspace_floats(int K, int D) {
-  if (K < 1 || K > 65535 || D < 2 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const size_t n = metrics_wide_layout(nullptr, D).total_floats(K);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
+int uglad_support_metrics_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 2, mw_pair_floats); }
 
 int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta, double* out, float* workspace, int K, int D, int beta,
                                uglad_stream_t stream) {
-  if (!true_theta || !pred_theta || !out || !workspace || (reinterpret_cast<size_t>(workspace) & 7)) return UGLAD_E_NULL;
+  if (!true_theta || !pred_theta || !out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
   if (uglad_support_metrics_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
   hipStream_t st = (hipStream_t)stream;
-  const MwView v = metrics_wide_layout(workspace, D).view;
+  const MwView v = mw_view(workspace, D);
   const dim3 tiles(v.tiles, K), wg(kWThreads);
   hipLaunchKernelGGL(mw_keys_kernel, dim3(v.nt, v.nt, K), wg, 0, st, true_theta, pred_theta, D, v);
   for (int pass = 0; pass < kMwPasses; ++pass) {  // (an even number of passes: the sorted keys end in buffer 0)

@@ -238,62 +238,3 @@ static NsLayout ns_layout(float* workspace, int M, int D) {
   l.Gh = l.W ? l.W + 2 * kNsSlabs * l.dslab : nullptr;
   return l;
 }
-
-// ---- workspace of the wide covariance front-end (cov_wide.h), per table, in DOUBLES (the buffer is 8-byte aligned; DP = D rounded up to 64):
-//   S64   DP x DP   the covariance in fp64, row stride DP, identity in the padding; repaired in place
-//   W     DP x DP   the Cholesky factor of S64 - sigma I under test: the tiles below the block diagonal (the diagonal tiles stay unfactored)
-//   mn | scale | mu   3 DP   the column statistics
-//   CovwCtl   8   the bisection's bracket, sigma, min eig and the flags (not PD, active, repaired)
-struct CovWideLayout {
-  int DP;
-  size_t table;  // doubles per table
-  CovwView view;
-  size_t total_floats(int K) const { return 2 * (size_t)K * table; }
-};
-static CovWideLayout cov_wide_layout(float* workspace, int D) {
-  CovWideLayout l{};
-  l.DP = (D + kCovwT - 1) / kCovwT * kCovwT;
-  l.table = covw_table_doubles(l.DP);
-  l.view = CovwView{reinterpret_cast<double*>(workspace), l.table, l.DP};
-  return l;
-}
-
-// ---- workspace of the wide conditional Gaussian (after_wide.h), per problem, in DOUBLES (8-byte aligned; DP = D rounded up to 64): the
-// factorisation's own layout first, so that its kernels serve both clients --
-//   A     DP x DP   the masked precision matrix, identity on the observed coordinates and in the padding
-//   L     DP x DP   its Cholesky factor: the tiles below the block diagonal
-//   r | y | t   3 DP   right-hand side, solution, intermediate (where the covariance keeps its column statistics)
-//   CovwCtl   8   only the "not PD" flag is live (sigma = 0, always active)
-// -- and behind it
-//   Wt    DP x DP   L^-T, block upper triangular
-//   log pivots | residual   2 DP
-//   parts of r   DP / 64 x DP   one row per block column of A
-struct AfterWideLayout {
-  int DP;
-  size_t problem;  // doubles per problem
-  AfterwView view;
-  size_t total_floats(int K) const { return 2 * (size_t)K * problem; }
-};
-static AfterWideLayout after_wide_layout(float* workspace, int D) {
-  AfterWideLayout l{};
-  l.DP = (D + kCovwT - 1) / kCovwT * kCovwT;
-  l.problem = afterw_problem_doubles(l.DP);
-  l.view = AfterwView{CovwView{reinterpret_cast<double*>(workspace), l.problem, l.DP}};
-  return l;
-}
-
-// ---- workspace of the wide support-recovery metrics (metrics_wide.h, MwView), per pair, in 4-byte words (8-byte aligned; every part even):
-//   keys 0 | keys 1   E = D (D - 1) / 2 words each, rounded up to even: the two buffers of the radix sort
-//   hist   16 x tiles   digit counts / offsets of the pass (tiles = E over kMwTile, rounded up)
-//   kpart  nt x nt x 4  the counts of the key kernel's tiles (nt = D over 64, rounded up)
-//   chunk  tiles x 4 | mw2   tiles int64 | ap   tiles fp64   the group statistics' records and partial sums
-struct MetricsWideLayout {
-  MwView view;
-  size_t total_floats(int K) const { return (size_t)K * view.pair; }
-};
-static MetricsWideLayout metrics_wide_layout(float* workspace, int D) {
-  MetricsWideLayout l{};
-  const int E = D * (D - 1) / 2, tiles = (E + kMwTile - 1) / kMwTile, nt = (D + kMwKeyTile - 1) / kMwKeyTile;
-  l.view = MwView{reinterpret_cast<unsigned*>(workspace), mw_pair_words((size_t)E, (size_t)tiles, (size_t)nt), E, tiles, nt};
-  return l;
-}

@@ -42,7 +42,7 @@ constexpr int kMwTile = kWThreads * kMwPer;    // keys per workgroup
 constexpr int kMwKeyTile = 64;                 // tile of the upper triangle in mw_keys_kernel
 static_assert(kWThreads == 256 && kMwBins * kMwBits == 64 && kMwPer < kMwBins, "a thread's digit counts share one 64-bit register");
 
-// One pair's part of the workspace in 4-byte words (every part even: the 64-bit parts stay 8-byte aligned; host_route.h, MetricsWideLayout):
+// One pair's part of the workspace in 4-byte words (the buffer is 8-byte aligned and every part even, so the 64-bit parts stay aligned):
 //   keys 0 | keys 1   E words each, rounded up to even: the sort's two buffers (the sorted keys end in buffer 0)
 //   hist   16 x tiles   digit counts of the pass, then their exclusive scan, (digit, tile) order
 //   kpart  nt x nt x 4  T, P, TP of every tile of mw_keys_kernel
@@ -63,6 +63,11 @@ struct MwView {
 __host__ __device__ constexpr size_t mw_pair_words(size_t E, size_t tiles, size_t nt) {
   return 2 * ((E + 1) & ~(size_t)1) + kMwBins * tiles + 4 * nt * nt + 4 * tiles + 2 * tiles + 2 * tiles;
 }
+__host__ inline MwView mw_view(float* workspace, int D) {
+  const int E = D * (D - 1) / 2, tiles = (E + kMwTile - 1) / kMwTile, nt = (D + kMwKeyTile - 1) / kMwKeyTile;
+  return MwView{reinterpret_cast<unsigned*>(workspace), mw_pair_words((size_t)E, (size_t)tiles, (size_t)nt), E, tiles, nt};
+}
+__host__ inline size_t mw_pair_floats(int D) { return mw_view(nullptr, D).pair; }
 
 // ---------------------------------------------------------------------------------------------------------------- workgroup helpers
 // (256 threads = 4 waves; s_w: 4 ints of LDS; the first barrier protects s_w's previous use)

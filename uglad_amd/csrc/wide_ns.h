@@ -289,6 +289,7 @@ __global__ __launch_bounds__(kWThreads) void ns_gemm64_kernel(NsBatch batch, siz
   }
 
   // ---- epilogue: acc[a][c][r] of lane l = C[i0 + wi + 16 a + (l >> 4) + 4 r][j0 + wj + 16 c + (l & 15)]
+  // (this kernel keeps its own loop, tuned per tile size; the layout is documented at chol_wide.h, t64_for_each_fragment)
   KSTAMP(14);
   double part = 0.0;
   if (EPI == kNsAffine) {
