@@ -101,6 +101,7 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
 #ifndef UGLAD_TRIDIAG_DPPSUM
 #define UGLAD_TRIDIAG_DPPSUM 0
 #endif
+  constexpr bool kFullLanes = 64 * NS <= DP;  // every lane slot of the chain wave is a row of the padded matrix: `lane + 64 s < DP` always holds
   constexpr bool kDppSum = UGLAD_TRIDIAG_DPPSUM && !UGLAD_TRIDIAG_ROWWAVES && (NT == 4 && TH == 512);
   constexpr bool kRowWaves = UGLAD_TRIDIAG_ROWWAVES && (NT == 4 && TH == 512);
   constexpr bool kPairSum = UGLAD_TRIDIAG_PAIRSUM && !kRowWaves && RG == 32 && (NCG % 2 == 0);  // (a wave = two column groups x 32 row groups)
@@ -279,17 +280,36 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
 #endif
       // ---- finish step k: p = tau A v, w = p - (tau/2)(p.v) v; v.(A v) was reduced per wave at the end of the last sweep
       float pv[NS], vv[NS], wl[NS];
+      // D <= 128 (two lane slots): lanes are masked by SELECTS on the values, not by branches around the LDS reads -- the reads of both slots are
+      // issued together and wait once, where every `if (row is live)` was an exec change, a skip branch and an LDS round trip of its own.  A
+      // lane slot is read whenever its index is inside the padded arrays (always, where the slots cover exactly the padded size), and a row that
+      // has left the trailing matrix gets its exact 0 from the select (its s_part entries are NOT zero).  Beyond D = 128 the chain is as it
+      // was: there the branch skips the whole gather of a lane slot whose 64 rows have all left, up to three of four slots, and the selects
+      // were slower (K = 8, D = 256, training pass: 30.4 ms before, 30.9 ms with them; profiles/tridiag_scalar_overhead.txt, section 9).
+      constexpr bool kChainSelects = DP <= 128;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const int rr = lane_k + 64 * s;
         float p = 0.f;
-        if (rr > k && lane + 64 * s < n) {
+        if constexpr (kChainSelects) {
+          float v = 0.f;
+          if (kFullLanes || lane + 64 * s < DP) {
 #pragma unroll 8
-          for (int g = 0; g < NPG; ++g) p += s_part[g * PS + rr];
-          p *= tau_k;
+            for (int g = 0; g < NPG; ++g) p += s_part[g * PS + rr];
+            p *= tau_k;
+            v = s_vec[ov + rr];
+          }
+          pv[s] = (rr > k && lane + 64 * s < n) ? p : 0.f;
+          vv[s] = v;
+        } else {
+          if (rr > k && lane + 64 * s < n) {
+#pragma unroll 8
+            for (int g = 0; g < NPG; ++g) p += s_part[g * PS + rr];
+            p *= tau_k;
+          }
+          pv[s] = p;
+          vv[s] = (lane + 64 * s < DP) ? s_vec[ov + rr] : 0.f;
         }
-        pv[s] = p;
-        vv[s] = (lane + 64 * s < DP) ? s_vec[ov + rr] : 0.f;
       }
       float vAv2[2] = {0.f, 0.f};
 #pragma unroll
@@ -309,7 +329,19 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const int c = lane_k + 64 * s;
-        x[s] = (lane + 64 * s < n) ? (s_vec[(3 + cur) * DP + c] - v_k1 * wl[s] - w_k1 * vv[s]) : 0.f;
+        if constexpr (kChainSelects) {
+          float xr = 0.f;
+          if (kFullLanes || lane + 64 * s < DP) {
+            // (ROUNDED products: while the expression sat behind the lane branch the two products of a lane slot were paired into one
+            // v_pk_mul_f32, which is never fused with the subtractions; left to contraction, the unconditional form becomes two v_fma_f32
+            // and the row differs in its last bit)
+#pragma clang fp contract(off)
+            xr = s_vec[(3 + cur) * DP + c] - v_k1 * wl[s] - w_k1 * vv[s];
+          }
+          x[s] = (lane + 64 * s < n) ? xr : 0.f;
+        } else {
+          x[s] = (lane + 64 * s < n) ? (s_vec[(3 + cur) * DP + c] - v_k1 * wl[s] - w_k1 * vv[s]) : 0.f;
+        }
       }
       const float dk1 = bcast_lane(pick(x, k1 >> 6), k1 & 63);
       if (k1 <= n - 3) {
@@ -327,7 +359,8 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
           // on the serial path of every step: hardware square root (1 ulp) and rcp + Newton divisions; tau and the scaling
           // come from the same rounded beta, so H stays orthogonal to rounding error.  (Tiny norms: library path.)
           const float nrm2 = fmaf(x0, x0, sig);
-          if (nrm2 > 1e-30f) {
+          // (D <= 128: the library path is laid out behind the loop body, not in the fall-through)
+          if (kChainSelects ? __builtin_expect(nrm2 > 1e-30f, 1) : nrm2 > 1e-30f) {
             beta = -copysignf(__builtin_amdgcn_sqrtf(nrm2), x0);
             const float dd = x0 - beta;  // |dd| >= |x0|: no cancellation
             sc = div_acc(1.0f, dd);
@@ -388,11 +421,21 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
       // nobody else to hide the latency); at D <= 128 the kernel is held to 64 VGPRs and four co-resident workgroups do
       // the hiding.
       constexpr int PB = (NT > 4) ? 8 : 1;
+      // The live column slots of a wave are a SUFFIX -- slot i holds columns up to cgmax + NCG i, live while that exceeds k1 -- so the first
+      // live one is computed ONCE per step, as a scalar, and a slot costs one scalar compare and branch; with the test
+      // `cgmax + NCG i > k1 && row_last > k` per slot the compiler built a lane mask for every slot, dead ones included (five scalar
+      // instructions each).  (k1 - cgmax + NCG >= 1.  UGLAD_TRIDIAG_ROWWAVES: a wave whose rows have all left the trailing matrix has no
+      // live slot.)  Not in the 1024-thread instantiations, which keep the test per slot: measured against the parent they gained nothing from
+      // it (D = 256, 160: +-0.5 %) or lost (D = 224: 608 -> 617 us per launch), where the 512-thread ones beyond D = 128 gain up to 7 %
+      // (profiles/tridiag_scalar_overhead.txt, section 9).
+      constexpr bool kFirstLiveSlot = TH <= 512;
+      const int i_first = (kRowWaves && row_last <= k) ? NC : (int)((unsigned)(k1 - cgmax + NCG) / (unsigned)NCG);
+      auto slot_live = [&](int i) { return kFirstLiveSlot ? i >= i_first : (cgmax + NCG * i > k1 && row_last > k); };
 #pragma unroll
       for (int i0 = 0; i0 < NC; i0 += PB) {
         // wave-uniform: some column of this batch is still in the trailing matrix -- and (D = 128 layout) some row of this wave:
         // rows <= k have left it, v, w and the next reflector vanish there
-        if (cgmax + NCG * (i0 + PB - 1) > k1 && row_last > k) {
+        if (slot_live(i0 + PB - 1)) {
           float vcv[PB], wcv[PB], ncv[PB];
 #pragma unroll
           for (int u = 0; u < PB; ++u) {
@@ -406,7 +449,7 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
 #pragma unroll
           for (int u = 0; u < PB; ++u) {
             const int i = i0 + u;
-            if (i < NC && cgmax + NCG * i > k1) {
+            if (i < NC && slot_live(i)) {
               const float vc = vcv[u], wc = wcv[u], nc = ncv[u];
               f4 t = (i < NL) ? s_a[i < NL ? i : 0][tid] : a[i < NC ? i : 0];
               t.x = t.x - vc * w4.x - wc * v4.x;
