@@ -310,7 +310,7 @@ def test_beyond_the_eigensolver_vs_oracle(emul, monkeypatch, ldl_launches):
 @pytest.mark.parametrize("ldl_launches", ["0", "1"])
 def test_logdet_and_inverse_of_indefinite_matrices_beyond_the_eigensolver(emul, monkeypatch, ldl_launches):
     """torch.logdet's rules without an eigensolver (main.py:307): finite for an even number of negative eigenvalues, NaN for an odd one;
-    the inverse (the loss's gradient S - Theta^-1) also for an indefinite matrix -- L D L^T carries the signs (chol.h)."""
+    the inverse (the loss's gradient S - Theta^-1) also for an indefinite matrix -- L D L^T carries the signs (ldl_wide.h)."""
     import uglad_amd
 
     monkeypatch.setenv("UGLAD_LDL_LAUNCHES", ldl_launches)

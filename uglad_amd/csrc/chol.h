@@ -10,7 +10,7 @@
 //   logdet A = sum log(pivot).
 // chol_inverse_packed (D <= 128, LDS): a pivot that is not > 0 (the matrix is indefinite, singular or holds a NaN) makes it return false;
 // the caller then flags the matrix and the eigen path computes it (torch.logdet's NaN / -inf rules live there).
-// ldl_inverse (D > 256, workspace slabs: wide_ns.h): the same scheme as A = L D L^T, any signs.
+// Beyond D = 128 (workspace slabs): the same scheme as A = L D L^T, any signs, in ldl_wide.h.
 #pragma once
 #include "glad_device.h"
 
@@ -205,197 +205,6 @@ __device__ __forceinline__ bool chol_inverse_packed(float* __restrict__ sP, floa
 __device__ __forceinline__ float chol_packed_at(const float* __restrict__ sP, int i, int j) {
   const int lo = i < j ? i : j, hi = i < j ? j : i;  // X[lo][hi], tile (lo >> 5, hi >> 5) in slot (hi >> 5, lo >> 5)
   return sP[chol_slot(hi >> 5, lo >> 5) * kTF + (lo & 31) * kTS + (hi & 31)];
-}
-
-// ---------------------------------------------------------------------------------------------------------------- L D L^T
-// The same blocked scheme WITHOUT the positivity requirement, for the sizes beyond the eigensolver (wide_ns.h), where no eigen path can
-// take over a matrix Cholesky refuses: A = L D L^T with unit lower triangular L and diagonal D of either sign (no pivoting), so that
-// log|det A| = sum log|d_i|, sign(det A) = parity of the negative d_i (torch.logdet's NaN for det < 0 comes from that), and
-// A^-1 = W^T D^-1 W with W = L^-1 -- also for an indefinite A, e.g. the Theta_L the reference itself produces at D = 512 with parameters
-// trained at D = 25 (10 of 512 eigenvalues negative, tests/golden/cell_d512_b1_L15_trained.npz).  For a positive definite matrix this
-// is Cholesky's arithmetic up to where the square roots sit.  A pivot that is zero or NaN returns false.
-//
-// One 32 x 32 diagonal block by one wave: L_jj (unit lower) -> sL, T = L_jj^-1 -> sW, the pivots -> dv[d0 .. d0 + 31].
-template <int LD>
-__device__ __forceinline__ bool ldl_diag_block(float* __restrict__ sL, float* __restrict__ sW, float* __restrict__ dv, int d0, float& log2sum,
-                                               int& negatives) {
-  const int lane = threadIdx.x & 63, r = lane & 31;
-  float b[32];
-#pragma unroll
-  for (int c = 0; c < 32; ++c) b[c] = sL[(d0 + r) * LD + d0 + c];
-  bool ok = true;
-  float mine = 1.f;
-#pragma unroll
-  for (int c = 0; c < 32; ++c) {
-    const float piv = bcast_lane(b[c], c);  // d_c
-    ok = ok && (piv != 0.f) && (piv == piv);
-    log2sum += __builtin_amdgcn_logf(fabsf(piv));
-    negatives += (piv < 0.f) ? 1 : 0;
-    if (r == c) mine = piv;
-    const float l = (r == c) ? 1.f : ((r > c) ? b[c] / piv : 0.f);  // column c of L
-    // a[r][c2] -= l[r][c] d_c l[c2][c], and d_c l[c2][c] is what lane c2 still holds in b[c]
-#pragma unroll
-    for (int c2 = c + 1; c2 < 32; ++c2) b[c2] = fmaf(-l, bcast_lane(b[c], c2), b[c2]);
-    b[c] = l;
-  }
-  float t[32];  // T = L^-1 (unit lower), lane = column q
-#pragma unroll
-  for (int i = 0; i < 32; ++i) {
-    float acc = (i == r) ? 1.f : 0.f;
-#pragma unroll
-    for (int k = 0; k < i; ++k) acc = fmaf(-bcast_lane(b[k], i), t[k], acc);
-    t[i] = acc;
-  }
-  if (lane < 32) {
-#pragma unroll
-    for (int c = 0; c < 32; ++c) sL[(d0 + r) * LD + d0 + c] = b[c];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) sW[(d0 + i) * LD + d0 + r] = t[i];
-    dv[d0 + r] = mine;
-  }
-  return ok;
-}
-
-// sL: the symmetric matrix (DP x DP, row stride DP + 1, identity on the padding) -> overwritten; sW: scratch of the same size; sX: the
-// result A^-1 (both triangles), same layout; dv: DP floats.  logabsdet and `negatives` (number of negative pivots = negative
-// eigenvalues) are uniform.  s_flag: one int, s_acc: two floats of LDS.  NW: waves of the workgroup (all of them call).
-template <int NT, int NW = kWaves>
-__device__ __forceinline__ bool ldl_inverse(float* __restrict__ sL, float* __restrict__ sW, float* __restrict__ sX, float* __restrict__ dv,
-                                            float& logabsdet, int& negatives, int* __restrict__ s_flag, float* __restrict__ s_acc, int nt = NT) {
-  // nt <= NT: the leading nt x nt tiles hold the matrix (the layout stays that of NT tiles); the padding is never touched
-  constexpr int DP = NT * 32, LD = DP + 1;
-  const int dp = nt * 32;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int li = lane & 31;
-  if (tid == 0) {
-    *s_flag = 1;
-    s_acc[0] = 0.f;
-    s_acc[1] = 0.f;
-  }
-  for (int idx = tid; idx < dp * dp; idx += (64 * NW)) sW[(idx / dp) * LD + idx % dp] = 0.f;
-  __syncthreads();
-  auto store_tile = [&](float* __restrict__ X, int I, int J, const f32x16& acc, float scale) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) X[(I * 32 + acc_row(e, lane)) * LD + J * 32 + li] = scale * acc[e];
-  };
-#pragma unroll 1
-  for (int j = 0; j < nt; ++j) {
-    if (w == 0) {
-      float l2 = 0.f;
-      int neg = 0;
-      const bool ok = ldl_diag_block<LD>(sL, sW, dv, 32 * j, l2, neg);
-      if (lane == 0) {
-        if (!ok) *s_flag = 0;
-        s_acc[0] += l2;
-        s_acc[1] += (float)neg;
-      }
-    }
-    __syncthreads();
-    if (*s_flag == 0) return false;  // (uniform)
-    // panel, i > j:  M_ij = A_ij T_jj^T (= L_ij D_j) -> sW(i, j);  L_ij = M_ij D_j^-1 -> sL(i, j)
-    for (int i = j + 1 + w; i < nt; i += NW) {
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-      mfma_tile(sL + (32 * i) * LD + 32 * j, LD, 1, sW + (32 * j) * LD + 32 * j, 1, LD, 32, acc);
-      const float invd = 1.0f / dv[32 * j + li];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int at = (i * 32 + acc_row(e, lane)) * LD + j * 32 + li;
-        sW[at] = acc[e];
-        sL[at] = acc[e] * invd;
-      }
-    }
-    __syncthreads();
-    {  // trailing update: A_ik -= M_ij L_kj^T for j < k <= i
-      const int nrem = nt - 1 - j, ntile = nrem * (nrem + 1) / 2;
-      for (int t = w; t < ntile; t += NW) {
-        int a = 0, rem = t;
-        while (rem > a) {
-          rem -= a + 1;
-          ++a;
-        }
-        const int i = j + 1 + a, k = j + 1 + rem;
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        mfma_tile(sW + (32 * i) * LD + 32 * j, LD, 1, sL + (32 * k) * LD + 32 * j, 1, LD, 32, acc);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sL[(i * 32 + acc_row(e, lane)) * LD + k * 32 + li] -= acc[e];
-      }
-    }
-    __syncthreads();
-  }
-  logabsdet = 0.69314718056f * s_acc[0];
-  negatives = (int)s_acc[1];
-  // ---- W = L^-1 in sW's lower tiles (the parked M_ij are dead; every tile is written before it is read)
-  constexpr int kPerD = NT > 1 ? (NT - 1 + NW - 1) / NW : 1;
-#pragma unroll 1
-  for (int d = 1; d < nt; ++d) {
-    f32x16 acc[kPerD];
-#pragma unroll
-    for (int n = 0; n < kPerD; ++n) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
-      const int j = w + NW * n, i = j + d;
-      if (i < nt) {
-        for (int k = j; k < i; ++k) mfma_tile(sL + (32 * i) * LD + 32 * k, LD, 1, sW + (32 * k) * LD + 32 * j, LD, 1, 32, acc[n]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < kPerD; ++n) {
-      const int j = w + NW * n, i = j + d;
-      if (i < nt) store_tile(sW, i, j, acc[n], 1.f);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < kPerD; ++n) {
-      const int j = w + NW * n, i = j + d;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
-      if (i < nt) mfma_tile(sW + (32 * i) * LD + 32 * i, LD, 1, sW + (32 * i) * LD + 32 * j, LD, 1, 32, acc[n]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < kPerD; ++n) {
-      const int j = w + NW * n, i = j + d;
-      if (i < nt) store_tile(sW, i, j, acc[n], -1.f);
-    }
-    __syncthreads();
-  }
-  // ---- V = D^-1 W (rows scaled) -> sL, lower tiles incl. the diagonal ones (L is dead)
-  for (int idx = tid; idx < dp * dp; idx += (64 * NW)) {
-    const int i = idx / dp, k = idx - i * dp;
-    if ((k >> 5) <= (i >> 5)) sL[i * LD + k] = sW[i * LD + k] / dv[i];
-  }
-  __syncthreads();
-  // ---- X = W^T V on the upper tiles, mirrored -> sX
-  {
-    const int ntile = nt * (nt + 1) / 2;
-    for (int t = w; t < ntile; t += NW) {
-      int I = 0, J = t;  // tile t -> (I <= J) over the nt x nt upper triangle, row by row
-      while (J >= nt - I) {
-        J -= nt - I;
-        ++I;
-      }
-      J += I;
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-      for (int k = J; k < nt; ++k) mfma_tile(sW + (32 * k) * LD + 32 * I, 1, LD, sL + (32 * k) * LD + 32 * J, LD, 1, 32, acc);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int i = I * 32 + acc_row(e, lane), jj = J * 32 + li;
-        if (i <= jj) {
-          sX[i * LD + jj] = acc[e];
-          sX[jj * LD + i] = acc[e];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  return true;
 }
 
 }  // namespace uglad

@@ -11,7 +11,7 @@
 //                         alone raises the flag on a pivot that is <= 0 or NaN (no atomics)
 // Whether the factorisation completes or breaks down decides "A - sigma I is positive definite" backward-stably (error <= D (D + 1) 2^-53
 // ||A||, Higham Thm 10.3) and without pivoting, since nothing past the first bad pivot is used.  Every launch returns at once for a slab that
-// is flagged or inactive (cholw_gate; the gated empties of ns_ldl_phase_kernel), so a sequence of factorisations needs no readback.
+// is flagged or inactive (cholw_gate), so a sequence of factorisations needs no readback.
 // L(j, j) itself is never stored over tile (j, j): no later launch of the factorisation reads it, and the other workgroups of the SAME panel
 // launch are still reading the tile it would replace.  A client that needs the diagonal factor asks for its inverse instead: on a
 // CholwInvView the diagonal tile's workgroup also runs the panel's solve on the identity and writes L(j, j)^-T and the 64 log-pivots into

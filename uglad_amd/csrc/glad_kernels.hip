@@ -39,6 +39,7 @@ namespace uglad {
 #include "wide_bwd.h"
 #include "wide_fwd.h"
 #include "wide_ns.h"
+#include "ldl_wide.h"
 #include "chol_wide.h"
 #include "cov_wide.h"
 #include "after_wide.h"

@@ -234,7 +234,14 @@ static int launch_cell_bwd_ns(const Route& r, hipStream_t st, const BwdStep& s, 
   return launch_status();
 }
 
-// out = (A + shift I)^-1 (and log det in the header) beyond the eigensolver's size: L D L^T of the padded matrix, two Newton steps
+// the slab layout of the L D L^T inverse (ldl_wide.h): f(std::integral_constant<int, ns_fact_dim(D)>)
+template <class F>
+static inline void ldl_layout(int D, F&& f) {
+  if (ns_fact_dim(D) == kNsFactSmall) return f(std::integral_constant<int, kNsFactSmall>{});
+  f(std::integral_constant<int, kNsMaxD>{});
+}
+
+// out = (A + shift I)^-1 (and log det in logdet_out) wherever Route::factor is kLdl: L D L^T of the padded matrix (ldl_wide.h), two Newton steps
 static void launch_ns_inverse(const Route& r, hipStream_t st, const float* A, const float* shift, int shift_stride, float* out, float* logdet_out,
                               float* workspace) {
   const int M = r.M, D = r.D, nt = wide_tiles(D), gs = r.gs, FD = ns_fact_dim(D), LDc = FD + 1;
@@ -242,14 +249,14 @@ static void launch_ns_inverse(const Route& r, hipStream_t st, const float* A, co
   float* X1 = l.W;                                 // the factorisation's first slab, dead once it returns (row stride FD + 1)
   float* X0 = l.W + 2 * (size_t)FD * (FD + 1);     // (row stride FD + 1)
   float* E = l.W + 3 * (size_t)FD * (FD + 1);      // residual, row stride D
-  const int ntl = (D + 31) / 32;
-  if (!r.ldl_phases) {
-    if (FD == kNsFactSmall)
-      hipLaunchKernelGGL(ns_ldl_kernel<kNsFactSmall>, dim3(M), dim3(64 * kNsLdlWaves), 0, st, A, shift, shift_stride, l.W, l.region, logdet_out, D, gs);
-    else
-      hipLaunchKernelGGL(ns_ldl_kernel<kNsMaxD>, dim3(M), dim3(64 * kNsLdlWaves), 0, st, A, shift, shift_stride, l.W, l.region, logdet_out, D, gs);
-  } else {
-    auto phase = [&](int ph, int jd, int items) {  // `items` tiles (one wave each) or elements (one thread each, capped) of work per matrix
+  ldl_layout(D, [&](auto fd) {  // (the kernels are instantiated per slab layout, ns_fact_dim)
+    constexpr int kFD = decltype(fd)::value;
+    if (!r.ldl_phases) {  // one workgroup per matrix walks the schedule
+      hipLaunchKernelGGL(ns_ldl_kernel<kFD>, dim3(M), dim3(64 * kNsLdlWaves), 0, st, A, shift, shift_stride, l.W, l.region, logdet_out, D, gs);
+      return;
+    }
+    // one launch per step: `items` tiles (one wave each) or elements (one thread each, capped) of work per matrix
+    ldl_schedule((D + 31) / 32, [&](int ph, int jd, int items) {
       int wgs = 1;
       if (ph == kLdlInit || ph == kLdlScale || ph == kLdlFinish) {
         wgs = (items + 64 * kLdlWavesPerWg - 1) / (64 * kLdlWavesPerWg);
@@ -258,30 +265,10 @@ static void launch_ns_inverse(const Route& r, hipStream_t st, const float* A, co
         wgs = (items + kLdlWavesPerWg - 1) / kLdlWavesPerWg;
       }
       if (wgs < 1) wgs = 1;
-      if (FD == kNsFactSmall)
-        hipLaunchKernelGGL(ns_ldl_phase_kernel<kNsFactSmall>, dim3(wgs, M), dim3(64 * kLdlWavesPerWg), 0, st, ph, jd, A, shift, shift_stride, l.W, l.region,
-                           logdet_out, D, gs);
-      else
-        hipLaunchKernelGGL(ns_ldl_phase_kernel<kNsMaxD>, dim3(wgs, M), dim3(64 * kLdlWavesPerWg), 0, st, ph, jd, A, shift, shift_stride, l.W, l.region,
-                           logdet_out, D, gs);
-    };
-    const int dpl = ntl * 32;
-    phase(kLdlInit, 0, dpl * dpl);
-    for (int j = 0; j < ntl; ++j) {
-      phase(kLdlDiag, j, 1);
-      if (j + 1 < ntl) {
-        phase(kLdlPanel, j, ntl - 1 - j);
-        phase(kLdlTrail, j, (ntl - 1 - j) * (ntl - j) / 2);
-      }
-    }
-    for (int d = 1; d < ntl; ++d) {
-      phase(kLdlWSum, d, ntl - d);
-      phase(kLdlWMul, d, ntl - d);
-    }
-    phase(kLdlScale, 0, dpl * dpl);
-    phase(kLdlX, 0, ntl * (ntl + 1) / 2);
-    phase(kLdlFinish, 0, dpl * dpl);
-  }
+      hipLaunchKernelGGL(ns_ldl_phase_kernel<kFD>, dim3(wgs, M), dim3(64 * kLdlWavesPerWg), 0, st, ph, jd, A, shift, shift_stride, l.W, l.region,
+                         logdet_out, D, gs);
+    });
+  });
   const WideFwd nofw{};
   const dim3 tiles(nt, nt, M), blk(kWThreads);
   // two Newton steps X <- X + X (I - A X): without pivoting the factorisation of a strongly indefinite matrix is only a starting point

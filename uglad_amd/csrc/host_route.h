@@ -19,7 +19,7 @@ using namespace uglad;
 #endif
 #endif
 #define UGLAD_MAX_EIG_DIM (32 * UGLAD_MAX_NT)  // the spectral path: eigensolver, LDS / slab-resident kernels templated on NT
-#define UGLAD_MAX_DIM (kNsMaxD > UGLAD_MAX_EIG_DIM ? kNsMaxD : UGLAD_MAX_EIG_DIM)  // beyond it the matrix-iteration path (wide_ns.h)
+#define UGLAD_MAX_DIM (kNsMaxD > UGLAD_MAX_EIG_DIM ? kNsMaxD : UGLAD_MAX_EIG_DIM)  // beyond the eigensolver: the matrix-iteration path (wide_ns.h, ldl_wide.h)
 // cond(b^T b + 4/lam I) up to which reference-made goldens sit inside the 1e-4 tolerance on Theta (tests/golden/regime_sweep.json:
 // every case up to cond 708 within 1.1e-5 of the fp64 value of its own function; the min-max-normalised fit that runs to convergence,
 // tests/golden/fit_direct_converged.npz, reaches 1.03e3 with precision_ 2.0e-5 from the reference; the case at 4.4e3 is 1.04e-4 off:
@@ -138,7 +138,7 @@ static Route make_route(int M, int D, int groups, bool training, int sqrt_mode) 
   // D = 160: 70 vs 216 us at M = 8, 315 vs 273 us at M = 256
   r.wide = D > 128 && (wide_mode >= 0 ? wide_mode == 1 : (D > 192 || M <= 128));
   r.cell = ns_cell(ns_mode, M, D, training, sqrt_mode) ? CellPath::kMatrixIteration : (r.wide ? CellPath::kWide : CellPath::kOneWorkgroup);
-  // Theta_0 and the loss on the factorisation of wide_ns.h (L D L^T + Newton steps) instead of the eigensolver: wherever there is none, and for
+  // Theta_0 and the loss on the factorisation of ldl_wide.h (L D L^T + Newton steps) instead of the eigensolver: wherever there is none, and for
   // the few large matrices the cell itself takes to the matrix-iteration path (one 256 x 256 matrix: 0.35 ms against 0.9 ms for the eigen
   // path's tridiagonalisation, merges, back-transformation and products).  D <= 128: blocked Cholesky (chol.h); the eigen path follows only
   // for matrices the Cholesky kernel flagged (not positive definite, NaN).
@@ -160,8 +160,8 @@ static Route make_route(int M, int D, int groups, bool training, int sqrt_mode) 
   r.ns_tile = tile == 32 || tile == 64 ? tile : (tiles < 256 ? 32 : 64);
   // the products' all-chunks-in-flight form (wide_ns.h, PRE): D <= 4 k chunks of the 32 x 32 tiling
   r.ns_prefetch_all = D <= 4 * NsTile<32>::kK && switch_on(kSwNsPrefetchAll);
-  // L D L^T: ONE workgroup per matrix up to D = 256 (0.35 ms there), a sequence of launches with the tiles of every phase spread over the
-  // chip beyond (ns_ldl_phase_kernel: 5 nt + 1 launches, nt = ceil(D / 32))
+  // L D L^T (ldl_wide.h: one schedule of phases, two kernels that walk it): ONE workgroup per matrix up to D = 256 (ns_ldl_kernel, 0.35 ms
+  // there), one launch per step with the tiles of the step spread over the chip beyond (ns_ldl_phase_kernel: 5 nt launches, nt = ceil(D / 32))
   const int ldl = switch_value(kSwLdlLaunches);
   r.ldl_phases = ldl >= 0 ? ldl != 0 : nt >= 9;
   return r;

@@ -1,5 +1,5 @@
-// The matrix-iteration path: the cell for matrices beyond the eigensolver's size (D > 256; uglad_set_matrix_iteration(1) forces it for
-// any D -- tests, A/B).  The reference has no size limit (glad.py:103-151): it computes the square root of b^T b + 4/lam I with ten
+// The matrix-iteration path: the cell for matrices beyond the eigensolver's size (D > 256, and few matrices of 128 < D <= 256:
+// host_route.h; uglad_set_matrix_iteration(1) forces it for any D -- tests, A/B).  The reference has no size limit (glad.py:103-151): it computes the square root of b^T b + 4/lam I with ten
 // Newton-Schulz steps of dense products and differentiates it with ten steps of an iterative Lyapunov solver (torch_sqrtm.py:13-46).
 // Up to D = 256 this library replaces both by an eigen-decomposition (the same function per eigenvalue); a
 // one-workgroup tridiagonalisation does not scale further, whereas dense products are what the chip is built for.  So here the cell IS
@@ -26,14 +26,12 @@
 // more -- the property the spectral path has by construction.  The square root travels from the forward to the backward pass in fp32, in
 // the slot that holds the eigenvectors on the spectral path (U), as the reference's backward starts from its fp32 square root.
 //
-// Theta_0 and the loss's logdet / inverse for D > 256: blocked L D L^T (chol.h) on slabs laid out for 1024, one workgroup per matrix
-// on three slabs of the workspace, then two Newton steps on tile products (fp32).  D carries the signs, so torch.logdet's rules (finite
-// for an even number of negative eigenvalues, NaN for an odd one) hold as on the spectral path; no pivoting.
+// Theta_0 and the loss's logdet / inverse on this path: the blocked L D L^T of ldl_wide.h on three slabs of the workspace, then two Newton
+// steps on tile products (fp32; launch_ns_inverse).  The products here are size-generic; what bounds D is that factorisation's layout.
 //
 // Workspace per matrix: the header of kWsPerMatrix floats the other paths use (partial sums, scalars) and a region of eight D x D fp64
 // slabs plus one fp32 slab (G_half).
 #pragma once
-#include "chol.h"
 #include "wide_bwd.h"
 
 namespace uglad {
@@ -42,12 +40,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kNsSlabs = 8;      // fp64 slabs per matrix
-// The products are size-generic; what bounds D is the layout of the L D L^T factorisation behind Theta_0 and the loss: three slabs of F x (F + 1)
-// floats per matrix, F = ns_fact_dim(D) -- 1024 up to D = 1024 (rounds 3's layout and timings: a row stride of 2049 floats for every D made the
-// factorisation of a 512 x 512 matrix 8 x slower, 17 ms, rows 64 cache lines apart), 2048 beyond (round 4: D up to 2048).
-constexpr int kNsMaxD = 2048;
-constexpr int kNsFactSmall = 1024;
-__host__ __device__ constexpr int ns_fact_dim(int D) { return D <= kNsFactSmall ? kNsFactSmall : kNsMaxD; }
 // offsets inside a matrix's header (floats), behind the backward's partial sums (wide_partial_floats): per-tile fp32 sums (the norm of
 // the forward cell, the loss's trace), then -- 8-byte aligned -- fp64: per-tile sums, four scalars, nt row-block maxima.  "Per tile" is
 // sized for the 32 x 32 tiling ((2 nt)^2 entries); the products run on 64 x 64 or 32 x 32 output tiles (ns_gemm64_kernel).
@@ -547,193 +539,6 @@ __global__ void ns_tile_sum_kernel(const float* __restrict__ hdr, size_t hdr_str
   float v = 0.f;
   for (int t = 0; t < nt * nt; ++t) v += hdr[(size_t)m * hdr_stride + ns_off_tiles(D) + t];
   out[m] = scale * v;
-}
-
-// ---- inverse and log-determinant beyond the eigensolver's size: L D L^T (chol.h) of the matrix padded to the next multiple of 32
-// (identity on the padding) on three workspace slabs of row stride FD + 1 (FD = ns_fact_dim(D)), one workgroup per matrix.  X0 = (src + shift I)^-1 is left in the third slab,
-// the log-determinant in logdet_out[m] with torch.logdet's rules (NaN for a negative determinant); a zero / NaN pivot leaves NaN in both.
-// The caller polishes X0 with Newton steps on tile products.
-constexpr int kNsLdlWaves = 16;  // operands live in L2 here, not LDS: a tile product is a round trip of latency, so 16 waves share the tiles
-template <int FD>
-__global__ __launch_bounds__(64 * kNsLdlWaves) void ns_ldl_kernel(const float* __restrict__ src, const float* __restrict__ shift, int shift_stride,
-                                                          float* __restrict__ slabs, size_t slab_stride, float* __restrict__ logdet_out, int D,
-                                                          int gs) {
-  constexpr int DP = FD, LD = DP + 1;
-  __shared__ int s_flag;
-  __shared__ float s_acc[2];
-  __shared__ float s_dv[DP];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  float* sL = slabs + (size_t)m * slab_stride;
-  float* sW = sL + (size_t)DP * LD;
-  float* sX = sW + (size_t)DP * LD;
-  const float* Am = src + (size_t)m * D * D;
-  const float sh = shift ? shift[(size_t)(m / gs) * shift_stride] : 0.f;
-  const int nt = (D + 31) / 32, dp = nt * 32;  // only the leading nt x nt tiles are factorised (identity on their padding)
-  for (int idx = tid; idx < dp * dp; idx += 64 * kNsLdlWaves) {
-    const int i = idx / dp, k = idx - i * dp;
-    sL[i * LD + k] = (i < D && k < D) ? Am[(size_t)i * D + k] + ((i == k) ? sh : 0.f) : ((i == k) ? 1.f : 0.f);
-  }
-  __syncthreads();
-  float logdet;
-  int neg;
-  const bool ok = ldl_inverse<FD / 32, kNsLdlWaves>(sL, sW, sX, s_dv, logdet, neg, &s_flag, s_acc, nt);
-  const float nan = __builtin_nanf("");
-  if (!ok) {
-    for (int idx = tid; idx < dp * dp; idx += 64 * kNsLdlWaves) sX[(idx / dp) * LD + idx % dp] = nan;
-    logdet = nan;
-  } else if (neg & 1) {
-    logdet = nan;  // torch.logdet of a matrix with negative determinant
-  }
-  if (tid == 0 && logdet_out) logdet_out[m] = logdet;
-}
-
-// ---- the same factorisation as a SEQUENCE OF LAUNCHES (round 4): ldl_inverse's phases, one launch each, the tiles of a phase dealt out over the waves
-// of as many workgroups as the phase has work for instead of over the 16 waves of one workgroup (D = 1024: 10.5 ms on one CU; the arithmetic is
-// 1 GFLOP).  A launch boundary is the barrier between phases; per 32-column block: the diagonal block (one wave), the panel, the trailing update;
-// then W = L^-1 diagonal by diagonal (two launches each), V = D^-1 W and X = W^T V.  Same tile products in the same order per tile as ldl_inverse:
-// the same bits.  acc4: four floats of scratch per matrix -- sum of log2 |pivot|, number of negative pivots, ok flag (1 = fine) -- zeroed by kLdlInit.
-enum { kLdlInit = 0, kLdlDiag, kLdlPanel, kLdlTrail, kLdlWSum, kLdlWMul, kLdlScale, kLdlX, kLdlFinish };
-constexpr int kLdlWavesPerWg = 4;
-template <int FD>
-__global__ __launch_bounds__(64 * kLdlWavesPerWg) void ns_ldl_phase_kernel(int phase, int jd, const float* __restrict__ src, const float* __restrict__ shift,
-                                                                           int shift_stride, float* __restrict__ slabs, size_t slab_stride,
-                                                                           float* __restrict__ logdet_out, int D, int gs) {
-  constexpr int DP = FD, LD = DP + 1;
-  const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 31;
-  const int gw = blockIdx.x * kLdlWavesPerWg + (tid >> 6), nw = gridDim.x * kLdlWavesPerWg;  // this wave among the launch's waves (per matrix)
-  float* sL = slabs + (size_t)m * slab_stride;
-  float* sW = sL + (size_t)DP * LD;
-  float* sX = sW + (size_t)DP * LD;
-  float* dv = sX + (size_t)DP * LD;  // the pivots and the four accumulators: the head of the region behind the three slabs (the Newton steps' residual,
-  float* acc4 = dv + DP;             // written only after the factorisation: >= D^2 > DP + 4 floats)
-  const int nt = (D + 31) / 32, dp = nt * 32;
-  auto store_tile = [&](float* __restrict__ X, int I, int J, const f32x16& acc, float scale) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) X[(I * 32 + acc_row(e, lane)) * LD + J * 32 + li] = scale * acc[e];
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  switch (phase) {
-    case kLdlInit: {
-      const float sh = shift ? shift[(size_t)(m / gs) * shift_stride] : 0.f;
-      const float* Am = src + (size_t)m * D * D;
-      for (int idx = blockIdx.x * blockDim.x + tid; idx < dp * dp; idx += gridDim.x * blockDim.x) {
-        const int i = idx / dp, k = idx - i * dp;
-        sL[i * LD + k] = (i < D && k < D) ? Am[(size_t)i * D + k] + ((i == k) ? sh : 0.f) : ((i == k) ? 1.f : 0.f);
-        sW[i * LD + k] = 0.f;
-      }
-      if (blockIdx.x == 0 && tid < 4) acc4[tid] = (tid == 2) ? 1.f : 0.f;
-      break;
-    }
-    case kLdlDiag: {  // one wave
-      if (gw != 0) break;
-      float l2 = 0.f;
-      int neg = 0;
-      const bool ok = ldl_diag_block<LD>(sL, sW, dv, 32 * jd, l2, neg);
-      if (lane == 0) {
-        acc4[0] += l2;
-        acc4[1] += (float)neg;
-        if (!ok) acc4[2] = 0.f;
-      }
-      break;
-    }
-    case kLdlPanel: {  // i > j:  M_ij = A_ij T_jj^T -> sW(i, j);  L_ij = M_ij D_j^-1 -> sL(i, j)
-      const int j = jd;
-      for (int i = j + 1 + gw; i < nt; i += nw) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        mfma_tile(sL + (32 * i) * LD + 32 * j, LD, 1, sW + (32 * j) * LD + 32 * j, 1, LD, 32, acc);
-        const float invd = 1.0f / dv[32 * j + li];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int at = (i * 32 + acc_row(e, lane)) * LD + j * 32 + li;
-          sW[at] = acc[e];
-          sL[at] = acc[e] * invd;
-        }
-      }
-      break;
-    }
-    case kLdlTrail: {  // A_ik -= M_ij L_kj^T for j < k <= i
-      const int j = jd, nrem = nt - 1 - j, ntile = nrem * (nrem + 1) / 2;
-      for (int t = gw; t < ntile; t += nw) {
-        int a = 0, rem = t;
-        while (rem > a) {
-          rem -= a + 1;
-          ++a;
-        }
-        const int i = j + 1 + a, k = j + 1 + rem;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        mfma_tile(sW + (32 * i) * LD + 32 * j, LD, 1, sL + (32 * k) * LD + 32 * j, 1, LD, 32, acc);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sL[(i * 32 + acc_row(e, lane)) * LD + k * 32 + li] -= acc[e];
-      }
-      break;
-    }
-    case kLdlWSum: {  // diagonal d of W = L^-1: sum_k L_ik W_kj -> sW(i, j) (reads diagonals < d only)
-      const int d = jd;
-      for (int j = gw; j + d < nt; j += nw) {
-        const int i = j + d;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        for (int k = j; k < i; ++k) mfma_tile(sL + (32 * i) * LD + 32 * k, LD, 1, sW + (32 * k) * LD + 32 * j, LD, 1, 32, acc);
-        store_tile(sW, i, j, acc, 1.f);
-      }
-      break;
-    }
-    case kLdlWMul: {  // W_ij = -T_ii (that sum)
-      const int d = jd;
-      for (int j = gw; j + d < nt; j += nw) {
-        const int i = j + d;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        mfma_tile(sW + (32 * i) * LD + 32 * i, LD, 1, sW + (32 * i) * LD + 32 * j, LD, 1, 32, acc);
-        UGLAD_WAVE_SYNC();  // (the tile is read by this wave alone and overwritten by it: every lane has its operands)
-        store_tile(sW, i, j, acc, -1.f);
-      }
-      break;
-    }
-    case kLdlScale: {  // V = D^-1 W (rows scaled) -> sL, lower tiles incl. the diagonal ones (L is dead)
-      for (int idx = blockIdx.x * blockDim.x + tid; idx < dp * dp; idx += gridDim.x * blockDim.x) {
-        const int i = idx / dp, k = idx - i * dp;
-        if ((k >> 5) <= (i >> 5)) sL[i * LD + k] = sW[i * LD + k] / dv[i];
-      }
-      break;
-    }
-    case kLdlX: {  // X = W^T V on the upper tiles, mirrored -> sX
-      const int ntile = nt * (nt + 1) / 2;
-      for (int t = gw; t < ntile; t += nw) {
-        int I = 0, J = t;
-        while (J >= nt - I) {
-          J -= nt - I;
-          ++I;
-        }
-        J += I;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-        for (int k = J; k < nt; ++k) mfma_tile(sW + (32 * k) * LD + 32 * I, 1, LD, sL + (32 * k) * LD + 32 * J, LD, 1, 32, acc);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int i = I * 32 + acc_row(e, lane), jj = J * 32 + li;
-          if (i <= jj) {
-            sX[i * LD + jj] = acc[e];
-            sX[jj * LD + i] = acc[e];
-          }
-        }
-      }
-      break;
-    }
-    default: {  // kLdlFinish: the log-determinant with torch.logdet's rules; NaN everywhere after a zero / NaN pivot
-      const bool ok = acc4[2] != 0.f;
-      const float nan = __builtin_nanf("");
-      if (!ok)
-        for (int idx = blockIdx.x * blockDim.x + tid; idx < dp * dp; idx += gridDim.x * blockDim.x) sX[(idx / dp) * LD + idx % dp] = nan;
-      if (blockIdx.x == 0 && tid == 0 && logdet_out)
-        logdet_out[m] = (!ok || (((int)acc4[1]) & 1)) ? nan : 0.69314718056f * acc4[0];
-      break;
-    }
-  }
 }
 
 // loss_partial[m] = -logdet[m] + trace term (wide_loss_trace_kernel's per-row-block sums at `off`)
