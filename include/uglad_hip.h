@@ -371,6 +371,27 @@ int uglad_support_metrics_wide_workspace_floats(int K, int D);
 int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta, double* out, float* workspace, int K, int D, int beta,
                                uglad_stream_t stream);
 
+/* The recovered graph of K precision (from_precision = 1) or partial-correlation (0) matrices, every 2 <= D <= uglad_max_dim(), many
+ * workgroups per problem (csrc/graph_wide.h): what graph_from_partial_correlations (main.py:825-946, called by viz_graph_from_precision,
+ * main.py:985-1005) builds edge by edge in a Python double loop, and the first six columns of compute_graph_statistics (main.py:1263-1300).
+ * Edges are the strict upper triangle in row-major order, E = D (D - 1) / 2, values read at [i][j], i < j; from a precision matrix
+ * rho_ij = -P[i][j] / sqrtf(P[i][i] * P[j][j]) in three correctly rounded fp32 operations (main.py:818-820 on a float32 precision_).
+ * Threshold per problem: n_keep[k] (HOST array; Python's int(sparsity * E), main.py:865) gives th = s[E - n_keep] with s = |rho| ascending,
+ * s[0] for n_keep = 0 (main.py:867: rho_upper[-0]); n_keep[k] = -1 takes threshold_in[k] (device; may be NULL when no entry is -1).  Edge
+ * (i, j) is kept iff rho_ij > th or rho_ij < -th (main.py:874, 892); NaN is never an edge and a NaN threshold keeps nothing.
+ * Outputs (device): threshold (K); edge_count (K) = m; edge_ij (K, E, 2) int32 and edge_w (K, E) fp32, the first m entries of a problem in
+ * the reference's order, the rest undefined (sign: w > th is "+"); degree (K, D) int32; with want_stats = 1 also triangles2 (K, D) int32,
+ * t_i = twice the triangles at node i, and stats (K, 6) DOUBLES = num_nodes, num_edges, avg_degree, density, avg_clustering, transitivity
+ * by the operations networkx performs on exact integers (one fp64 division each; the c_i summed in node order) -- with want_stats = 0 both
+ * may be NULL and the triangle product is not launched.  Results do not depend on K or on the problem's place in the batch.  One chain of
+ * at most 32 + ceil(K / 64) launches, no host readback.  workspace: uglad_graph_wide_workspace_floats(K, D) floats, 8-byte aligned
+ * (UGLAD_E_NULL otherwise).  K <= 65535.  UGLAD_E_DIM for a dimension or an n_keep outside [-1, E], UGLAD_E_MODE for a flag that is not
+ * 0 / 1, all checked before any launch; the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+int uglad_graph_wide_workspace_floats(int K, int D);
+int uglad_graph_wide(const float* values, int from_precision, const int* n_keep, const float* threshold_in, float* threshold,
+                     int* edge_count, int* edge_ij, float* edge_w, int* degree, int* triangles2, double* stats, int want_stats, int K, int D,
+                     float* workspace, uglad_stream_t stream);
+
 /* The same decomposition by two-sided cyclic Jacobi (round-robin ordering, Rutishauser rotations): slower, independent of
  * the divide & conquer solver; beta comes back unsorted.  Cross-check only. */
 int uglad_symeig_jacobi(const float* A, float* U, float* beta, int M, int D, uglad_stream_t stream);

@@ -20,6 +20,10 @@ from .main import (  # noqa: F401
     mean_imputation,
     get_partial_correlations,
     device_report_metrics,
+    recovered_graph,
+    graph_from_partial_correlations,
+    compute_graph_statistics,
+    RecoveredGraph,
     conditional_gaussian_batch,
     conditional_gaussian_with_probabilities,
     compute_map_estimate,

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -73,6 +73,9 @@ _SIGS = {
     "uglad_support_metrics_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_support_metrics_wide": ([_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_void_p], ctypes.c_int),
+    "uglad_graph_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_graph_wide": ([_c_float_p, ctypes.c_int, ctypes.c_void_p, _c_float_p] + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                         _c_float_p, ctypes.c_void_p], ctypes.c_int),
     "uglad_set_wide_mode": ([ctypes.c_int], ctypes.c_int),
     "uglad_glad_backward_wrt_s": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + [_c_float_p] * 13
                                   + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
@@ -84,6 +87,17 @@ EXPORTS = tuple(_SIGS)
 
 class UgladError(RuntimeError):
     pass
+
+
+class GraphWide(NamedTuple):
+    """What uglad_graph_wide leaves on the device for K problems (include/uglad_hip.h)."""
+    threshold: torch.Tensor            # (K,) float32
+    edge_count: torch.Tensor           # (K,) int32: m
+    edge_ij: torch.Tensor              # (K, E, 2) int32, the first m rows defined
+    edge_w: torch.Tensor               # (K, E) float32, the first m defined
+    degree: torch.Tensor               # (K, D) int32
+    triangles2: Optional[torch.Tensor]  # (K, D) int32: twice the triangles at every node
+    stats: Optional[torch.Tensor]      # (K, 6) float64: num_nodes, num_edges, avg_degree, density, avg_clustering, transitivity
 
 
 class HipLib:
@@ -398,6 +412,43 @@ class HipLib:
         wsp = self._wide_workspace("uglad_support_metrics_wide", K, D, pred_theta.device)
         out = torch.empty(K, 11, dtype=torch.float64, device=pred_theta.device)
         self._call("uglad_support_metrics_wide", tp, pp, self._vp(out), self._p(wsp), K, D, int(beta))
+        return out
+
+    def graph_wide(self, values, n_keep=None, threshold=None, from_precision: bool = True, want_stats: bool = True) -> "GraphWide":
+        """uglad_graph_wide, every 2 <= D <= max_dim: (K,D,D) fp32 precision matrices (or partial correlations with `from_precision=False`)
+        -> the recovered graphs as device tensors (GraphWide).  Per problem either `n_keep` (an int or K of them: the number of largest
+        |rho| the threshold is ranked by, 0 <= n_keep <= E) or `threshold` (a float, K of them or a (K,) tensor); with both, the problems
+        whose n_keep is -1 take the threshold.  Only the first edge_count[k] rows of edge_ij[k] / edge_w[k] are defined."""
+        if values.dim() != 3 or values.shape[1] != values.shape[2]:
+            raise UgladError("graph_wide: a tensor of shape (K, D, D)")
+        K, D, _ = values.shape
+        vp = self._p(values)
+        dev = values.device
+        E = D * (D - 1) // 2
+        if n_keep is None:
+            if threshold is None:
+                raise UgladError("graph_wide: n_keep or threshold")
+            keep = [-1] * K
+        else:
+            keep = [int(n_keep)] * K if isinstance(n_keep, int) else [int(n) for n in n_keep]
+        if len(keep) != K:
+            raise UgladError("graph_wide: one n_keep per problem")
+        th_in = None
+        if threshold is not None:
+            th_in = torch.as_tensor(threshold, dtype=torch.float32).reshape(-1).expand(K) if not torch.is_tensor(threshold) or threshold.numel() == 1 \
+                else threshold.reshape(-1)
+            if th_in.numel() != K:
+                raise UgladError("graph_wide: one threshold per problem")
+            th_in = th_in.to(device=dev, dtype=torch.float32).contiguous()
+        wsp = self._wide_workspace("uglad_graph_wide", K, D, dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = GraphWide(threshold=torch.empty(K, dtype=torch.float32, device=dev), edge_count=torch.empty(K, **i32),
+                        edge_ij=torch.empty(K, E, 2, **i32), edge_w=torch.empty(K, E, dtype=torch.float32, device=dev),
+                        degree=torch.empty(K, D, **i32), triangles2=torch.empty(K, D, **i32) if want_stats else None,
+                        stats=torch.empty(K, 6, dtype=torch.float64, device=dev) if want_stats else None)
+        self._call("uglad_graph_wide", vp, int(bool(from_precision)), (ctypes.c_int * K)(*keep), self._p(th_in), self._p(out.threshold),
+                   self._vp(out.edge_count), self._vp(out.edge_ij), self._p(out.edge_w), self._vp(out.degree), self._vp(out.triangles2),
+                   self._vp(out.stats), int(bool(want_stats)), K, D, self._p(wsp))
         return out
 
     def symeig(self, A, U, beta, jacobi: bool = False):

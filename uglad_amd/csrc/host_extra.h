@@ -218,6 +218,50 @@ int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta,
   return launch_status();
 }
 
+int uglad_graph_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 2, gw_problem_floats); }
+
+int uglad_graph_wide(const float* values, int from_precision, const int* n_keep, const float* threshold_in, float* threshold,
+                     int* edge_count, int* edge_ij, float* edge_w, int* degree, int* triangles2, double* stats, int want_stats, int K, int D,
+                     float* workspace, uglad_stream_t stream) {
+  if (!values || !n_keep || !threshold || !edge_count || !edge_ij || !edge_w || !degree || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_graph_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
+  if ((from_precision != 0 && from_precision != 1) || (want_stats != 0 && want_stats != 1)) return UGLAD_E_MODE;
+  if (want_stats && (!triangles2 || !stats)) return UGLAD_E_NULL;
+  const GwView v = gw_view(workspace, D);
+  bool ranked = false;
+  for (int k = 0; k < K; ++k) {
+    if (n_keep[k] < -1 || n_keep[k] > v.s.E) return UGLAD_E_DIM;
+    if (n_keep[k] == -1 && !threshold_in) return UGLAD_E_NULL;
+    ranked = ranked || n_keep[k] >= 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int nt = v.s.nt;
+  const dim3 sort_tiles(v.s.tiles, K), tiles(nt, nt, K), wg(kWThreads);
+  if (ranked) {  // (a batch of given thresholds needs no order)
+    hipLaunchKernelGGL(gw_keys_kernel, tiles, wg, 0, st, values, from_precision, v);
+    for (int pass = 0; pass < kMwPasses; ++pass) {  // (an even number of passes: the sorted keys end in buffer 0)
+      hipLaunchKernelGGL(mw_hist_kernel, sort_tiles, wg, 0, st, pass, pass & 1, v.s);
+      hipLaunchKernelGGL(mw_scan_kernel, dim3(K), wg, 0, st, v.s);
+      hipLaunchKernelGGL(mw_scatter_kernel, sort_tiles, wg, 0, st, pass, pass & 1, v.s);
+    }
+  }
+  for (int k0 = 0; k0 < K; k0 += kGwKeepPer) {
+    GwKeep keep;
+    const int n = K - k0 < kGwKeepPer ? K - k0 : kGwKeepPer;
+    for (int q = 0; q < kGwKeepPer; ++q) keep.n[q] = q < n ? n_keep[k0 + q] : -1;
+    hipLaunchKernelGGL(gw_threshold_kernel, dim3(n), dim3(64), 0, st, keep, k0, threshold_in, threshold, v);
+  }
+  hipLaunchKernelGGL(gw_row_kernel, dim3(v.DP, K), wg, 0, st, values, from_precision, degree, v);
+  hipLaunchKernelGGL(gw_scan_kernel, dim3(K), wg, 0, st, edge_count, v);
+  hipLaunchKernelGGL(gw_edges_kernel, dim3(D, K), wg, 0, st, values, from_precision, edge_ij, edge_w, v);
+  if (want_stats) {
+    hipLaunchKernelGGL(gw_triangles_kernel, tiles, wg, 0, st, v);
+    hipLaunchKernelGGL(gw_rowsum_kernel, dim3((D + kWThreads - 1) / kWThreads, K), wg, 0, st, triangles2, v);
+    hipLaunchKernelGGL(gw_finish_kernel, dim3(K), wg, 0, st, degree, triangles2, stats, v);
+  }
+  return launch_status();
+}
+
 int uglad_tridiagonalize(const float* A0, const float* A1, const float* lam, float* R, float* workspace, int M, int D,
                          uglad_stream_t stream) {
   if (!A0 || !R || !workspace || (A1 && !lam)) return UGLAD_E_NULL;

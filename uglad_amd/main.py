@@ -663,6 +663,12 @@ class uGLAD_GL(object):
             print(f"Total runtime: {time() - start} secs\n")
         return compare_theta
 
+    def recovered_graph(self, sparsity: float = 0.1):
+        """The graph of the fitted precision_ (recovered_graph): the `sparsity` fraction of the edges with the largest |rho|."""
+        if self.precision_ is None:
+            raise ValueError("call fit() first")
+        return recovered_graph(self.precision_, sparsity=sparsity)
+
     def predict(self, X=None, S=None) -> np.ndarray:
         """Inference-only pass: the trained 42 parameters applied to new data (no_grad forward, the reference's
         main.py:539-540 pattern).  Give a samples table X (processed like `fit` does) or covariance(s) S.
@@ -713,6 +719,12 @@ class uGLAD_multitask(object):
         if verbose:
             print(f"Total runtime: {time() - start} secs\n")
         return compare_theta
+
+    def recovered_graph(self, sparsity: float = 0.1):
+        """The K graphs of the fitted precision_ (recovered_graph): the `sparsity` fraction of the edges with the largest |rho|."""
+        if self.precision_ is None:
+            raise ValueError("call fit() first")
+        return recovered_graph(self.precision_, sparsity=sparsity)
 
     def predict(self, Xb=None, S=None) -> np.ndarray:
         """no_grad forward of the trained model on new tables (list) or covariances (K, D, D)."""
@@ -783,6 +795,193 @@ def get_partial_correlations(precision):
     idx = np.arange(P.shape[-1])
     rho[..., idx, idx] = 1.0
     return rho
+
+
+# -------------------------------------------------------------------------------------------- the recovered graph
+GRAPH_STAT_KEYS = ("num_nodes", "num_edges", "avg_degree", "density", "avg_clustering", "transitivity", "diameter", "avg_shortest_path")
+
+
+class RecoveredGraph(object):
+    """One recovered graph: `edges` (m, 2) int32 with i < j in row-major order, `weights` (m,) -- the partial correlation of every edge
+    (float32 from the device, float64 from the host formulation) -- `threshold`, `degree` (D,), `triangles` (D,) (None without stats) and
+    `stats`, a dict with the keys of the reference's compute_graph_statistics (diameter and avg_shortest_path None: networkx's to give)."""
+
+    __slots__ = ("edges", "weights", "threshold", "degree", "triangles", "stats")
+
+    def __init__(self, edges, weights, threshold, degree, triangles, stats):
+        self.edges, self.weights, self.threshold, self.degree, self.triangles, self.stats = edges, weights, threshold, degree, triangles, stats
+
+    @property
+    def positive(self) -> np.ndarray:
+        """(m,) bool: the edge's sign ("+", the reference's green: rho > th)."""
+        return self.weights > self.threshold
+
+
+def _stats_dict(six) -> dict:
+    d = {"num_nodes": int(six[0]), "num_edges": int(six[1])}
+    d.update({key: float(x) for key, x in zip(GRAPH_STAT_KEYS[2:6], six[2:6])})
+    d["diameter"] = d["avg_shortest_path"] = None
+    return d
+
+
+def _n_keep(sparsity, D: int) -> int:
+    E = D * (D - 1) // 2
+    n = int(sparsity * E)  # (ref main.py:865)
+    if not 0 <= n <= E:
+        raise ValueError(f"sparsity {sparsity} keeps {n} of {E} edges")
+    return n
+
+
+def _recovered_graph_host(values, from_precision: bool, n_keep, threshold, stats: bool) -> RecoveredGraph:
+    """uglad_graph_wide's definitions for ONE (D, D) matrix on the host in float64, vectorised (sort, compare, (A A) o A): for a host array
+    whose values float32 cannot hold -- rounding could merge a value with the threshold -- and for sizes the device does not cover."""
+    V = np.asarray(values, dtype=np.float64)
+    D = V.shape[-1]
+    i, j = np.triu_indices(D, 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = -V[i, j] / np.sqrt(V[i, i] * V[j, j]) if from_precision else V[i, j]
+    if n_keep is None:
+        th = np.float64(threshold)
+    else:
+        s = np.sort(np.abs(rho))
+        th = s[len(s) - n_keep] if n_keep > 0 else s[0]  # (the reference's rho_upper[-0])
+    keep = (rho > th) | (rho < -th)
+    ei, ej = i[keep], j[keep]
+    A = np.zeros((D, D))
+    A[ei, ej] = A[ej, ei] = 1.0
+    degree = A.sum(axis=1).astype(np.int64)
+    triangles = st = None
+    if stats:
+        t2 = ((A @ A) * A).sum(axis=1).astype(np.int64)  # (exact: integers below 2^53)
+        triangles = t2 // 2
+        st = _stats_dict(_six_statistics(D, int(keep.sum()), degree, t2))
+    return RecoveredGraph(np.stack([ei, ej], axis=1).astype(np.int32), rho[keep], th, degree, triangles, st)
+
+
+def _six_statistics(D: int, m: int, degree, t2):
+    """The operations networkx performs (density, average_clustering, transitivity), in its order, on Python integers."""
+    d = [int(x) for x in degree]
+    t = [int(x) for x in t2]
+    c = [0 if ti == 0 else ti / (di * (di - 1)) for di, ti in zip(d, t)]
+    return (D, m, sum(d) / D, m / (D * (D - 1)) * 2, sum(c) / D, 0 if sum(t) == 0 else sum(t) / sum(di * (di - 1) for di in d))
+
+
+def _fits_float32(a: np.ndarray) -> bool:
+    if a.dtype == np.float32:
+        return True
+    with np.errstate(over="ignore", invalid="ignore"):
+        back = a.astype(np.float32).astype(a.dtype)
+    return bool(np.all((back == a) | (a != a)))
+
+
+def _recovered_graphs(values, from_precision: bool, n_keep, threshold, stats: bool):
+    """K graphs of a (K, D, D) device tensor or host array: on the device wherever float32 holds the values (uglad_graph_wide), else by
+    the host formulation."""
+    lib = _lib.get_lib()
+    on_device = torch.is_tensor(values) and values.device.type != "cpu"
+    host = None if on_device else np.asarray(values.detach() if torch.is_tensor(values) else values)
+    K, D = int(values.shape[0]), int(values.shape[-1])
+    if D < 2 or D > lib.max_dim or not (on_device or _fits_float32(host)):
+        host = values.detach().cpu().numpy() if on_device else host
+        return [_recovered_graph_host(host[k], from_precision, n_keep, threshold, stats) for k in range(K)]
+    V = values.detach() if on_device else torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32))
+    V = V.to(device=_lib.device(), dtype=torch.float32).contiguous()
+    g = lib.graph_wide(V, n_keep=n_keep, threshold=None if n_keep is not None else threshold, from_precision=from_precision, want_stats=stats)
+    count = g.edge_count.cpu().numpy()
+    th, degree = g.threshold.cpu().numpy(), g.degree.cpu().numpy()
+    t2, six = (g.triangles2.cpu().numpy(), g.stats.cpu().numpy()) if stats else (None, None)
+    out = []
+    for k in range(K):
+        m = int(count[k])
+        out.append(RecoveredGraph(g.edge_ij[k, :m].cpu().numpy(), g.edge_w[k, :m].cpu().numpy(), th[k], degree[k],
+                                  t2[k] // 2 if stats else None, _stats_dict(six[k]) if stats else None))
+    return out
+
+
+def recovered_graph(precision, sparsity: float = 0.1, threshold=None, stats: bool = True):
+    """The graph a precision matrix stands for (ref main.py:985-1005: partial correlations, then the `sparsity` fraction of the edges
+    with the largest |rho|; or every edge beyond a given `threshold`), with degrees, triangle counts and the statistics of the reference's
+    compute_graph_statistics, all computed on the device (uglad_graph_wide).  (D, D) or (K, D, D), a numpy array or a device tensor ->
+    a RecoveredGraph or a list of K.  No networkx: graph_from_partial_correlations builds its nx.Graph from the same edge list."""
+    single = len(precision.shape) == 2
+    P = precision[None] if single else precision
+    n_keep = None if threshold is not None else _n_keep(sparsity, int(P.shape[-1]))
+    out = _recovered_graphs(P, True, n_keep, threshold, stats)
+    return out[0] if single else out
+
+
+def graph_from_partial_correlations(rho, names, sparsity=1, title="", fig_size=12, PLOT=True, save_file=None, roundOFF=5):
+    """The reference's graph_from_partial_correlations (main.py:825-946), same arguments and return values: (nx.Graph with every node
+    of `names` and the kept edges -- attributes color, weight rounded to `roundOFF` decimals, label -- , the PNG bytes of its drawing or
+    None without PLOT, the edge list as strings).  The threshold, the membership test and the edge order come from uglad_graph_wide instead
+    of a Python loop over D^2 entries: a device tensor stays on the device, a host array goes there when float32 holds its values
+    exactly, and is otherwise evaluated on the host in float64 (rounding could merge values with the threshold)."""
+    import networkx as nx
+
+    names = list(names)
+    D = int(rho.shape[-1])
+    g = _recovered_graphs(rho[None], False, _n_keep(sparsity, D), None, False)[0]
+    G = nx.Graph()
+    G.add_nodes_from(names)
+    edge_strings = []
+    for (i, j), w, plus in zip(g.edges.tolist(), g.weights, g.positive):
+        colour, w = ("green", "+") if plus else ("red", "-"), round(np.float64(w), roundOFF)
+        G.add_edge(names[i], names[j], color=colour[0], weight=w, label=colour[1])
+        edge_strings.append(f"({names[i]}, {names[j]}, {w}, {colour[0]})")
+    return G, _draw_graph(G, title, fig_size, save_file) if PLOT else None, edge_strings
+
+
+def _draw_graph(G, title, fig_size, save_file):
+    """PNG bytes of a spring layout of G: grey nodes with their names just above them, edges in their colour, as wide as |weight| relative
+    to the largest."""
+    import io
+
+    import matplotlib.pyplot as plt
+    import networkx as nx
+
+    colours = [c for _, _, c in G.edges(data="color")]
+    widths = np.abs(np.array([w for _, _, w in G.edges(data="weight")], dtype=np.float64))
+    if widths.size:
+        widths = widths / widths.max()
+    fig = plt.figure(figsize=(fig_size, fig_size))
+    try:
+        ax = fig.gca()
+        where = nx.spring_layout(G, scale=0.2, k=1.0 / np.sqrt(G.number_of_edges() + 10))
+        nx.draw_networkx_nodes(G, where, node_color="grey", node_size=100, ax=ax)
+        nx.draw_networkx_edges(G, where, edge_color=colours, width=widths, ax=ax)
+        nx.draw_networkx_labels(G, {node: (x, y + 0.008) for node, (x, y) in where.items()}, ax=ax)
+        ax.set_title(str(title), fontsize=20)
+        ax.margins(0.15)
+        fig.tight_layout()
+        if save_file:
+            fig.savefig(save_file, bbox_inches="tight")
+        png = io.BytesIO()
+        fig.savefig(png)
+        return png.getvalue()
+    finally:
+        plt.close(fig)
+
+
+def compute_graph_statistics(G):
+    """The reference's compute_graph_statistics (main.py:1263-1300): a one-row DataFrame with num_nodes, num_edges, avg_degree, density,
+    avg_clustering, transitivity, diameter, avg_shortest_path.  The first six are counted on the device from G's adjacency matrix
+    (uglad_graph_wide with the threshold 0.5: degrees, the triangle product); the last two are all-pairs searches and stay networkx's,
+    for a connected graph only.  A graph the device does not cover (fewer than 2 or more than max_dim nodes, self-loops, directed or
+    parallel edges) is networkx's as a whole."""
+    import networkx as nx
+    import pandas as pd
+
+    D = G.number_of_nodes()
+    if D < 2 or D > _lib.get_lib().max_dim or G.is_directed() or G.is_multigraph() or nx.number_of_selfloops(G):
+        row = {"num_nodes": D, "num_edges": G.number_of_edges(), "avg_degree": sum(dict(G.degree()).values()) / D if D > 0 else 0,
+               "density": nx.density(G), "avg_clustering": nx.average_clustering(G), "transitivity": nx.transitivity(G)}
+    else:
+        A = nx.to_numpy_array(G, dtype=np.float32, weight=None)
+        row = _recovered_graphs(A[None], False, None, 0.5, True)[0].stats
+    connected = nx.is_connected(G)
+    row["diameter"] = nx.diameter(G) if connected else None
+    row["avg_shortest_path"] = nx.average_shortest_path_length(G) if connected else None
+    return pd.DataFrame([{key: row[key] for key in GRAPH_STAT_KEYS}])
 
 
 # Smallest D > max_eig_dim that goes to uglad_conditional_mean_wide; below it (and above max_eig_dim) the host formulation would run.  0: the
