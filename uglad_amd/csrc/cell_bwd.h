@@ -24,8 +24,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
   constexpr int DP = NT * 32, LD = DP + 1;
   UGLAD_BIG_BUFFERS(sX, DP * LD, sY, DP * LD, gws)  // U ; G -> G_half -> T -> C o F -> T2
   __shared__ float s_beta[DP], s_r[DP];
-  __shared__ __attribute__((aligned(16))) float s_a[kNsIters][DP];  // NS10: a_i^(t) ...
-  __shared__ __attribute__((aligned(16))) float s_q[kNsIters][DP];  // ... and its square
+  __shared__ __attribute__((aligned(16))) float s_a0[DP], s_aN[DP];  // NS10: a_i^(0) and a_i^(10), all that K_ij needs (ns_divided_difference)
   __shared__ float s_red[8];
   __shared__ float s_g[kWaves][kNRho + 1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -42,6 +41,38 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
   float g[kNRho];
 #pragma unroll
   for (int q = 0; q < kNRho; ++q) g[q] = 0.f;
+  // The upper-triangle entries of a thread (entry e = tid + kThreads q, as in the forward cell) are the same in every step.  DP <= 128: they are
+  // worked out once, here, into s_ent[q][tid] = (i << 8) | j, 0xffff where there is none ([q][tid]: a wave reads 64 consecutive shorts), and
+  // phase A and the G_out assembly of every step read them back in the order q = 0, 1, ... they were walked in -- the summation order of the 28
+  // rhoNN sums and of dL/dlam.  Beyond (66 KB of table), the walk is redone in each of the two phases.
+  constexpr int kMaxQ = ((DP / 2) * (DP + 1) + kThreads - 1) / kThreads;
+  constexpr bool kPre = DP <= 128;          // all entries of a thread in registers at once
+  constexpr int kQ = kPre ? kMaxQ : 8;      // entries per thread and pass
+  constexpr int kIShift = kPre ? 8 : 16, kJMask = (1 << kIShift) - 1;
+  const int D1 = D + 1, total = ((D + 1) / 2) * D1;
+  const int sp = kThreads / D1, sc = kThreads - sp * D1;
+  auto entry = [&](int e, int p, int c) -> int {  // (i << kIShift) | j of entry (pair p, offset c), -1 when there is none
+    if (e >= total) return -1;
+    if (c < D - p) return (p << kIShift) | (p + c);
+    const int i = D - 1 - p;
+    return (i == p) ? -1 : ((i << kIShift) | (i + (c - (D - p))));
+  };
+  auto advance = [&](int& p, int& c) {
+    c += sc;
+    p += sp;
+    if (c >= D1) {
+      c -= D1;
+      ++p;
+    }
+  };
+  __shared__ unsigned short s_ent[kPre ? kMaxQ : 1][kPre ? kThreads : 1];
+  if constexpr (kPre) {
+    int p = tid / D1, c = tid - p * D1;
+    for (int q = 0; q < kMaxQ; ++q) {
+      s_ent[q][tid] = (unsigned short)entry(tid + kThreads * q, p, c);  // (read back by this thread alone: no barrier)
+      advance(p, c);
+    }
+  }
 #pragma unroll 1
   for (int s = 0; s < k_count; ++s) {
     const bool first = (s == 0), last = (s == k_count - 1);
@@ -179,55 +210,62 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
     const float nrmR = sqrtf(block_sum(r2, s_red));
     if (mode == UGLAD_SQRT_NS10 && tid < DP) {
       float a = s_r[tid] / nrmR;
+      s_a0[tid] = a;
 #pragma unroll
-      for (int it = 0; it < kNsIters; ++it) {
-        s_a[it][tid] = a;
-        s_q[it][tid] = a * a;
-        a = 0.5f * a * (3.f - a * a);
-      }
+      for (int it = 0; it < kNsIters; ++it) a = 0.5f * a * (3.f - a * a);
+      s_aN[tid] = a;
     }
     __syncthreads();
 
     KSTAMP(1);
     // ---- phase A: rhoNN + threshold backward on the upper triangle (entry e = tid + kThreads q, as in the forward cell)
     using TU = Tiles<NT, true>;
-    constexpr int kMaxQ = ((DP / 2) * (DP + 1) + kThreads - 1) / kThreads;
-    constexpr bool kPre = DP <= 128;          // all entries of a thread in registers at once
-    constexpr int kQ = kPre ? kMaxQ : 8;      // entries per thread and pass
-    const int D1 = D + 1, total = ((D + 1) / 2) * D1;
-    const int sp = kThreads / D1, sc = kThreads - sp * D1;
-    const int p0 = tid / D1, c0 = tid - p0 * D1;
-    auto entry = [&](int e, int p, int c) -> int {  // (i << 16) | j of entry (pair p, offset c), -1 when there is none
-      if (e >= total) return -1;
-      if (c < D - p) return (p << 16) | (p + c);
-      const int i = D - 1 - p;
-      return (i == p) ? -1 : ((i << 16) | (i + (c - (D - p))));
-    };
-    auto advance = [&](int& p, int& c) {
-      c += sc;
-      p += sp;
-      if (c >= D1) {
-        c -= D1;
-        ++p;
-      }
-    };
+    [[maybe_unused]] const int p0 = tid / D1, c0 = tid - p0 * D1;  // where this thread's walk starts (DP > 128 only: below, the table)
     float gz[kQ];  // dL/dZ_in, direct part (through rhoNN's third input); DP > 128: parked in G_out's upper triangle instead
     {
-      int p = p0, c = c0;
+      [[maybe_unused]] int p = p0, c = c0;
       for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
         int pk[kQ];
         float hx[kQ], zz[kQ], gn[kQ], sv[kQ];
+        if constexpr (kPre) {
+          // the pass's indices together, then every operand from a clamped address with the value selected afterwards: 32-bit offsets
+          // (load_at), no branch per entry, the two LDS reads of every G entry issued before the first of them is waited for
 #pragma unroll
-        for (int u = 0; u < kQ; ++u) {
-          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
-          advance(p, c);
-          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
-          const bool in = pk[u] >= 0;
-          if (kPre) gz[u] = 0.f;
-          hx[u] = in ? Hm[i * D + j] : 0.f;
-          zz[u] = in ? Zm[i * D + j] : 0.f;
-          sv[u] = in ? Sm[i * D + j] : 0.f;
-          gn[u] = in ? ((i == j) ? sY[i * LD + j] : 0.5f * (sY[i * LD + j] + sY[j * LD + i])) : 0.f;
+          for (int u = 0; u < kQ; ++u) pk[u] = (int)(short)s_ent[u][tid];
+          float gt[kQ];
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
+            const bool in = pk[u] >= 0;
+            const unsigned at = in ? 4u * ((unsigned)i * (unsigned)D + (unsigned)j) : 0u;
+            gz[u] = 0.f;
+            hx[u] = load_at<float>(Hm, at);
+            zz[u] = load_at<float>(Zm, at);
+            sv[u] = load_at<float>(Sm, at);
+            gn[u] = sY[opaque_v(in ? i * LD + j : 0)];  // (opaque: left visible, the select becomes a branch around the two reads)
+            gt[u] = sY[opaque_v(in ? j * LD + i : 0)];
+          }
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
+            const bool in = pk[u] >= 0;
+            hx[u] = in ? hx[u] : 0.f;
+            zz[u] = in ? zz[u] : 0.f;
+            sv[u] = in ? sv[u] : 0.f;
+            gn[u] = in ? ((i == j) ? gn[u] : 0.5f * (gn[u] + gt[u])) : 0.f;
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
+            advance(p, c);
+            const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
+            const bool in = pk[u] >= 0;
+            hx[u] = in ? Hm[i * D + j] : 0.f;
+            zz[u] = in ? Zm[i * D + j] : 0.f;
+            sv[u] = in ? Sm[i * D + j] : 0.f;
+            gn[u] = in ? ((i == j) ? sY[i * LD + j] : 0.5f * (sY[i * LD + j] + sY[j * LD + i])) : 0.f;
+          }
         }
         // forward activations of two entries at a time on the packed fp32 pipe, the backward entry by entry (packed, its 28
         // accumulators would need a second set of registers that the kernel does not have)
@@ -244,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
           for (int c2 = 0; c2 < 2; ++c2) {
             const int u = c2 ? u1 : u0;
             if ((c2 == 0 || has1) && pk[u] >= 0) {
-              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
               const RhoAct act = act2.half(c2);
               const float x = hx[u];
               const bool active = fabsf(x) > act.rho;
@@ -292,13 +330,9 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
           int I, J;
           TU::ij(t, I, J);
           const int j = J * 32 + (lane & 31);
-          float aj[kNsIters], qj[kNsIters];
-#pragma unroll
-          for (int it = 0; it < kNsIters; ++it) {
-            aj[it] = s_a[it][j];
-            qj[it] = s_q[it][j];
-          }
+          const float a0j = s_a0[j], aNj = s_aN[j];
           const float rj = s_r[j], bj = s_beta[j];
+          const float inv_2nrmR = 1.0f / (2.f * nrmR);
 #pragma unroll
           for (int e4 = 0; e4 < 4; ++e4) {  // accumulator entries 4 e4 .. 4 e4 + 3 sit in four consecutive rows
             const int i0 = I * 32 + 8 * e4 + 4 * (lane >> 5);
@@ -307,19 +341,12 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
 #pragma unroll
               for (int r = 0; r < 4; ++r) Kr[r] = 1.0f / (s_r[i0 + r] + rj);
             } else {
-              float P[4] = {1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-              for (int it = 0; it < kNsIters; ++it) {  // one 16-byte LDS read per iterate covers the four rows
-                const f4 a4 = *reinterpret_cast<const f4*>(&s_a[it][i0]);
-                const f4 q4 = *reinterpret_cast<const f4*>(&s_q[it][i0]);
-                P[0] *= 0.5f * (3.f - q4.x - qj[it] + a4.x * aj[it]);
-                P[1] *= 0.5f * (3.f - q4.y - qj[it] + a4.y * aj[it]);
-                P[2] *= 0.5f * (3.f - q4.z - qj[it] + a4.z * aj[it]);
-                P[3] *= 0.5f * (3.f - q4.w - qj[it] + a4.w * aj[it]);
-              }
-              const float sc = 1.0f / (2.f * nrmR);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) Kr[r] = P[r] * sc;
+              const f4 a0 = *reinterpret_cast<const f4*>(&s_a0[i0]);  // one 16-byte LDS read covers the four rows
+              const f4 aN = *reinterpret_cast<const f4*>(&s_aN[i0]);
+              Kr[0] = ns_divided_difference(a0.x, a0j, aN.x, aNj, inv_2nrmR);
+              Kr[1] = ns_divided_difference(a0.y, a0j, aN.y, aNj, inv_2nrmR);
+              Kr[2] = ns_divided_difference(a0.z, a0j, aN.z, aNj, inv_2nrmR);
+              Kr[3] = ns_divided_difference(a0.w, a0j, aN.w, aNj, inv_2nrmR);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -371,7 +398,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
     __syncthreads();
     KSTAMP(20);
     {
-      int p = p0, c = c0;
+      [[maybe_unused]] int p = p0, c = c0;
       for (int q0 = 0; q0 < kMaxQ; q0 += kQ) {
         // all reads of a pass first, then the writes: G_out goes into G_B's own buffer, and read / write / read / ... of one LDS array
         // is a chain of waits the compiler cannot reorder (19 k instead of 12 k ticks for this phase)
@@ -379,10 +406,14 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
         float gb[kQ], sij[kQ];
 #pragma unroll
         for (int u = 0; u < kQ; ++u) {
-          pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
-          advance(p, c);
+          if constexpr (kPre) {
+            pk[u] = (int)(short)s_ent[u][tid];
+          } else {
+            pk[u] = (q0 + u < kMaxQ) ? entry(tid + kThreads * (q0 + u), p, c) : -1;
+            advance(p, c);
+          }
           const bool in = pk[u] >= 0;
-          const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+          const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
           gb[u] = sY[in ? i * LD + j : 0];  // (unconditional reads, clamped addresses: no branch per entry)
           // S_ij again from memory (L2: phase A read it this step) rather than 33 more registers held across the four products, which
           // spilled dL/dZ's direct part (21 VGPRs, reloaded one round trip at a time right here: 8 k ticks)
@@ -396,7 +427,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
 #pragma unroll
           for (int u = 0; u < kQ; ++u) {
             const bool in = pk[u] >= 0;
-            const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+            const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
             const float o = gz[u] - gb[u];
             sY[in ? i * LD + j : DP] = o;  // in G_B's place: (i, j) is read by this thread alone, (j, i) by nobody (G_B lives on the upper triangle)
             sY[in ? j * LD + i : DP] = o;
@@ -406,7 +437,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
 #pragma unroll
           for (int u = 0; u < kQ; ++u) {
             if (pk[u] >= 0) {
-              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
               const float o = Go[i * D + j] - gb[u];
               sY[i * LD + j] = o;
               sY[j * LD + i] = o;
@@ -420,7 +451,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
 #pragma unroll
           for (int u = 0; u < kQ; ++u) {
             if (pk[u] >= 0) {
-              const int i = pk[u] >> 16, j = pk[u] & 0xffff;
+              const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
               const float v = fmaf(gb[u], inv_lam, gS[base + i * D + j]);
               gS[base + i * D + j] = v;
               gS[base + j * D + i] = v;

@@ -338,6 +338,16 @@ __device__ __forceinline__ float sqrt_spectrum(float beta, float c, float nrmA, 
   return y * sqrtf(nrmA);
 }
 
+// K_ij of NS10's backward: the divided difference of the reference's ten Newton-Schulz steps on R / ||R|| between eigenvalues i and j,
+//   K_ij = prod_{t<10} 1/2 (3 - (a_i^t)^2 - (a_j^t)^2 + a_i^t a_j^t) / (2 ||R||),      a^{t+1} = 1/2 a^t (3 - (a^t)^2),  a^0 = r / ||R||.
+// Since a_i^{t+1} + a_j^{t+1} = 1/2 (a_i^t + a_j^t) (3 - (a_i^t)^2 + a_i^t a_j^t - (a_j^t)^2), factor t is (a_i^{t+1} + a_j^{t+1}) / (a_i^t + a_j^t)
+// and the product telescopes to (a_i^10 + a_j^10) / (a_i^0 + a_j^0): two adds and a division from the first and the last iterate.  Every a
+// is positive (0 < a^0 <= 1 stays in (0, 1]; padded rows carry r = 1), so nothing cancels and no denominator is zero; in fp32 the quotient
+// is closer to the fp64 product than the ten-factor product was (tests/test_ns_divided_difference.py).  inv_2nrmR = 1 / (2 ||R||).
+__device__ __forceinline__ float ns_divided_difference(float a0_i, float a0_j, float aN_i, float aN_j, float inv_2nrmR) {
+  return div_acc(aN_i + aN_j, a0_i + a0_j) * inv_2nrmR;
+}
+
 // ------------------------------------------------------------------------------------------ shifted spectral form
 // theta_half = f(b) is NOT assembled as U diag(phi(beta)) U^T: with trained parameters b = S/lam - Z is negative definite with
 // |beta| ~ 20..300 while r(beta) - |beta| ~ 0.1..1, i.e. phi(beta) = -beta + (small), and the fp32 eigensolver's ~1e-6 ||b|| error in

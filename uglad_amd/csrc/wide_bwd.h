@@ -149,8 +149,7 @@ __global__ __launch_bounds__(kWThreads) void wide_gemm_kernel(
   __shared__ double s_dbl[EPI == kEpiThetaHalf ? 3 * kWMaxD + 80 : 1];
   if ((EPI == kEpiThetaHalf || EPI == kEpiInverse || EPI == kEpiNewton) && blockIdx.y > blockIdx.x) return;  // (symmetric: upper tiles only; uniform per workgroup)
   __shared__ float s_beta[EPI == kEpiDivDiff ? kWMaxD : 1], s_r[EPI == kEpiDivDiff ? kWMaxD : 1];
-  __shared__ float s_a[EPI == kEpiDivDiff ? kNsIters : 1][EPI == kEpiDivDiff ? 2 * kWT : 1];  // NS10: a^(t) of [0..63] rows, [64..127] columns
-  __shared__ float s_q[EPI == kEpiDivDiff ? kNsIters : 1][EPI == kEpiDivDiff ? 2 * kWT : 1];  // ... and its square
+  __shared__ float s_a0[EPI == kEpiDivDiff ? 2 * kWT : 1], s_aN[EPI == kEpiDivDiff ? 2 * kWT : 1];  // NS10: a^(0), a^(10) of [0..63] rows, [64..127] columns
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int m = blockIdx.z, I = blockIdx.y, J = blockIdx.x;
   const float* A = Ag + (size_t)m * a_stride;
@@ -195,12 +194,10 @@ __global__ __launch_bounds__(kWThreads) void wide_gemm_kernel(
     if (mode == UGLAD_SQRT_NS10 && tid < 2 * kWT) {
       const int idx = (tid < kWT) ? i0 + tid : j0 + tid - kWT;
       float a = ((idx < D) ? s_r[idx] : 1.f) / nrmR;
+      s_a0[tid] = a;
 #pragma unroll
-      for (int it = 0; it < kNsIters; ++it) {
-        s_a[it][tid] = a;
-        s_q[it][tid] = a * a;
-        a = 0.5f * a * (3.f - a * a);
-      }
+      for (int it = 0; it < kNsIters; ++it) a = 0.5f * a * (3.f - a * a);
+      s_aN[tid] = a;
     }
   }
 
@@ -290,13 +287,7 @@ __global__ __launch_bounds__(kWThreads) void wide_gemm_kernel(
         if (mode == UGLAD_SQRT_EXACT) {
           K = 1.0f / (s_r[i] + rj);
         } else {
-          float P = 1.f;
-#pragma unroll
-          for (int it = 0; it < kNsIters; ++it) {
-            const float ai = s_a[it][il], aj = s_a[it][kWT + wj + li];
-            P *= 0.5f * (3.f - s_q[it][il] - s_q[it][kWT + wj + li] + ai * aj);
-          }
-          K = P * (1.0f / (2.f * nrmR));
+          K = ns_divided_difference(s_a0[il], s_a0[kWT + wj + li], s_aN[il], s_aN[kWT + wj + li], 1.0f / (2.f * nrmR));
         }
         const float cij = acc[e];
         if (i == j) glam = fmaf(cij, -2.f * K * inv_lam2, glam);
