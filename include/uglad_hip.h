@@ -306,6 +306,30 @@ int uglad_covariance_wide_workspace_floats(int K, int D);
 int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, double eval_offset, float* S_out, double* min_eig_out,
                           float* workspace, uglad_stream_t stream);
 
+/* The association matrix of K tables that mix categorical and real columns, and the reference's repair on it (csrc/assoc_wide.h; replaces
+ * prepare_data.py:253-285 pairwise_cov_matrix with :177-209 cramers_v -- bias-corrected Cramer's V, Yates' correction on a 2 x 2 table as
+ * scipy's chi2_contingency applies it -- for c/c pairs, :212-250 correlation_ratio for c/r pairs and Pearson's r for r/r pairs, and
+ * :347-352, the repair of get_covariance).  table is a DEVICE pointer to (K, N, D) row-major FP64 tables, encoded: a categorical column
+ * holds level codes 0 .. card - 1, a real column its values.  The five maps are DEVICE int arrays that describe the expanded layout the
+ * K tables share (one column per level, one per real column; uglad_amd.utils.prepare_data.encode_mixed_table makes them):
+ * col_feature[W] (-1: padding), col_level[W] (>= 0 a level, -1 a real column, -2 padding), feat_offset[D], feat_width[D] -- a feature's
+ * expanded columns never straddle a multiple of 64 -- and tile_first[W / 64 + 1], the first feature of every 64 expanded columns (the last
+ * entry is D).  W is a multiple of 64, D <= W <= UGLAD_ASSOC_MAX_WIDTH.  A level without a row in a table is ignored there, as pd.crosstab
+ * ignores it.  A_out (K, D, D) fp32 receives the matrix, exactly symmetric; A64_out (K, D, D) fp64, optional, the same before the one
+ * rounding and ALWAYS unrepaired.  min_eig_out NULL: no repair.  Otherwise (K doubles): a table whose smallest eigenvalue is <= 1e-6 gets
+ * A_out += (eval_offset - min eig) I and min_eig_out[k] = that eigenvalue, found by 48 bisection steps on "A - sigma I has a Cholesky
+ * factorisation" over [-||A||_inf, 1e-6] (the matrix is indefinite: V and eta are >= 0, r is signed) to ||A||_inf 2^-48; a table that
+ * passes at 1e-6 gets +infinity.  Many workgroups per table, 3 + 50 + 49 * 2 ceil(D / 64) + 1 launches, no host readback.  A NaN in a
+ * real column gives NaN in that feature's row and column only (without repair).  workspace: uglad_association_workspace_floats(K, D, W)
+ * floats, 8-byte aligned (UGLAD_E_NULL otherwise).  2 <= D <= uglad_max_dim(), N >= 2, K <= 65535 (UGLAD_E_DIM otherwise, as for a W
+ * that is no multiple of 64 or out of range); the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+#define UGLAD_ASSOC_MAX_WIDTH 16384
+int uglad_association_max_width(void);
+int uglad_association_workspace_floats(int K, int D, int W);
+int uglad_association(const double* table, int K, int N, int D, const int* col_feature, const int* col_level, const int* feat_offset,
+                      const int* feat_width, const int* tile_first, int W, double eval_offset, float* A_out, double* A64_out,
+                      double* min_eig_out, float* workspace, uglad_stream_t stream);
+
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
  * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k; workspace receives d, e, tau
  * (3 x 32*ceil(D/32) floats per matrix).  uglad_cell_fwd / uglad_symeig / uglad_init_theta / uglad_loss_fwd launch this

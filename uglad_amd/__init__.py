@@ -21,6 +21,7 @@ from .main import (  # noqa: F401
     get_partial_correlations,
     device_report_metrics,
     recovered_graph,
+    mixed_association,
     graph_from_partial_correlations,
     compute_graph_statistics,
     RecoveredGraph,
@@ -30,5 +31,6 @@ from .main import (  # noqa: F401
     save_uGLAD_model,
     load_uGLAD_model,
 )
+from .utils.prepare_data import cramers_v, correlation_ratio, pairwise_cov_matrix, encode_mixed_table  # noqa: F401
 
 __version__ = "0.1.0"

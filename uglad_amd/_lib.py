@@ -9,6 +9,7 @@ import ctypes
 import os
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +63,10 @@ _SIGS = {
     "uglad_covariance_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_covariance_wide": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_float_p,
                                ctypes.c_void_p, _c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_association_max_width": ([], ctypes.c_int),
+    "uglad_association_workspace_floats": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_association": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_double,
+                           _c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p], ctypes.c_int),
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
@@ -358,6 +363,30 @@ class HipLib:
         if return_min_eig:
             return S, mn, ~torch.isinf(mn)
         return S
+
+    def association(self, table64, maps, eval_offset: float = 0.1, repair: bool = True, want_f64: bool = False):
+        """(K,N,D) FLOAT64 encoded mixed tables on the device + the MixedMaps of their expanded layout
+        (utils.prepare_data.encode_mixed_table) -> (A, min_eig, A64) (uglad_association): A (K,D,D) fp32 -- Cramer's V, the correlation
+        ratio and Pearson's r, repaired like a covariance when `repair` --, min_eig (K,) fp64 (the smallest eigenvalue before the repair,
+        +inf for a table that needed none; None without `repair`), A64 (K,D,D) fp64 unrepaired (None without `want_f64`)."""
+        self._require_f64(table64, 3, "association takes a contiguous (K, N, D) float64 tensor")
+        K, N, D = table64.shape
+        W = int(maps.W)
+        if len(maps.feat_offset) != D:
+            raise UgladError(f"association: the maps describe {len(maps.feat_offset)} features, the table has {D}")
+        dev = table64.device
+        n = int(self._dll.uglad_association_workspace_floats(K, D, W))
+        if n < 0:
+            self._check("uglad_association_workspace_floats", n)
+        wsp = torch.empty(n, dtype=torch.float32, device=dev)
+        ints = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+                for a in (maps.col_feature, maps.col_level, maps.feat_offset, maps.feat_width, maps.tile_first)]
+        A = torch.empty(K, D, D, dtype=torch.float32, device=dev)
+        A64 = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_f64 else None
+        mn = torch.empty(K, dtype=torch.float64, device=dev) if repair else None
+        self._call("uglad_association", self._vp(table64), K, N, D, *[self._vp(a) for a in ints], W, float(eval_offset), self._p(A),
+                   self._vp(A64), self._vp(mn), self._p(wsp))
+        return A, mn, A64
 
     def conditional_mean(self, precision, mean, observed, values, clip01: bool = False):
         """uglad_conditional_mean: (K,D,D), (K,D), (K,D) mask, (K,D) -> full_mean (K,D), cond_cov (K,D,D), log_pdf (K)."""

@@ -42,6 +42,7 @@ namespace uglad {
 #include "ldl_wide.h"
 #include "chol_wide.h"
 #include "cov_wide.h"
+#include "assoc_wide.h"
 #include "after_wide.h"
 #include "metrics_wide.h"
 #include "graph_wide.h"

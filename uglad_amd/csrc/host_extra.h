@@ -96,6 +96,39 @@ int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, d
   return launch_status();
 }
 
+int uglad_association_max_width(void) { return UGLAD_ASSOC_MAX_WIDTH; }
+static_assert(UGLAD_ASSOC_MAX_WIDTH == kAssocMaxWidth, "the header's constant is the kernels'");
+
+int uglad_association_workspace_floats(int K, int D, int W) {
+  if (K < 1 || K > 65535 || D < 2 || D > UGLAD_MAX_DIM || W < D || W > kAssocMaxWidth || W % kT64) return UGLAD_E_DIM;
+  const size_t n = (size_t)K * 2 * assoc_table_doubles(t64_padded(D), W);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+
+int uglad_association(const double* table, int K, int N, int D, const int* col_feature, const int* col_level, const int* feat_offset,
+                      const int* feat_width, const int* tile_first, int W, double eval_offset, float* A_out, double* A64_out,
+                      double* min_eig_out, float* workspace, uglad_stream_t stream) {
+  if (!table || !col_feature || !col_level || !feat_offset || !feat_width || !tile_first || !A_out || !wide_workspace_ok(workspace))
+    return UGLAD_E_NULL;
+  if (uglad_association_workspace_floats(K, D, W) < 0 || N < 2) return UGLAD_E_DIM;  // (N = 1: the bias correction divides by N - 1)
+  hipStream_t st = (hipStream_t)stream;
+  const CholwView v = assoc_view(workspace, D, W);
+  const AssocMaps m{col_feature, col_level, feat_offset, feat_width, tile_first, W};
+  const int wt = W / kT64;
+  hipLaunchKernelGGL(assoc_stats_kernel, dim3(wt, K), dim3(kWThreads), 0, st, table, N, D, m, v);
+  hipLaunchKernelGGL(assoc_gram_kernel, dim3(wt, wt, K), dim3(kWThreads), 0, st, table, N, D, m, v, A64_out, A_out);
+  if (!min_eig_out) return launch_status();  // no repair
+  // as uglad_covariance_wide: the test at the threshold, then the bisection -- on the bracket of an indefinite matrix
+  hipLaunchKernelGGL(assoc_rowsum_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, v);
+  for (int step = 0; step <= kAssocSteps; ++step) {
+    hipLaunchKernelGGL(assoc_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, v);
+    launch_cholw(st, K, v);
+  }
+  hipLaunchKernelGGL(assoc_control_kernel, dim3(K), dim3(64), 0, st, kAssocSteps, D, v);
+  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, v, A_out, min_eig_out);
+  return launch_status();
+}
+
 #ifdef UGLAD_PHASE_EXIT
 int uglad_diag_set_exit(int at) {  // (development build: see glad_device.h)
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_exit_at), &at, sizeof(int));

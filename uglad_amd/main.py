@@ -201,6 +201,17 @@ def _covariance(Xb, eval_offset):
     return _to_dev(prepare_data.get_covariance(Xb, offset=eval_offset))
 
 
+def mixed_association(df, dtype, repair: bool = True, eval_offset: float = 0.1):
+    """The association matrix of a table that mixes categorical ('c') and real ('r') columns, on the device (uglad_association,
+    csrc/assoc_wide.h; the reference's pairwise_cov_matrix, prepare_data.py:253-285): `dtype` maps column name -> 'c' | 'r'.  Returns
+    (A, min_eig): A the (D, D) fp32 matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset -
+    min eig) I, prepare_data.py:347-352), and min_eig the smallest eigenvalue before the repair as a float (+inf where none was needed;
+    None without `repair`)."""
+    table, maps = prepare_data.encode_mixed_table(df, dtype)
+    A, mn, _ = _lib.get_lib().association(torch.from_numpy(table[None]).to(_lib.device()), maps, eval_offset=eval_offset, repair=repair)
+    return A[0], (None if mn is None else float(mn[0]))
+
+
 def _print_every(EPOCHS: int) -> int:
     return max(1, int(EPOCHS / 10))
 
@@ -221,10 +232,13 @@ def _allreduce_grads(model, loss, coll: Collective):
 
 # ============================================================================================ drivers
 def run_uGLAD_direct(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, INIT_DIAG=0, L=15, VERBOSE=True,
-                     sqrt_mode=None):
+                     sqrt_mode=None, Sb=None):
     """Direct mode: one table, one covariance, EPOCHS Adam steps on the glasso loss (ref main.py:338-425).
-    Passing trueTheta adds the reference's log-cosh structure penalty to the loss (main.py:398)."""
-    Sb = _covariance(Xb, eval_offset)
+    Passing trueTheta adds the reference's log-cosh structure penalty to the loss (main.py:398).
+    Sb (additive): the (B, D, D) fp32 input matrices already on the device -- Xb is then not looked at (fit_mixed: the association
+    matrix of a mixed table takes the covariance's place)."""
+    if Sb is None:
+        Sb = _covariance(Xb, eval_offset)
     if trueTheta is not None:
         trueTheta = _to_dev(trueTheta)
     B = Sb.shape[0]
@@ -659,6 +673,42 @@ class uGLAD_GL(object):
         self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
         # regime diagnostic (additive): the largest cond(b^T b + 4/lambda I) any pass of this fit saw; warns beyond the validated bound
         self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit", get_collective() if mode == "missing" else None)  # (the sharded mode)
+        if verbose:
+            print(f"Total runtime: {time() - start} secs\n")
+        return compare_theta
+
+    def fit_mixed(self, df, dtype, true_theta=None, eval_offset=0.1, epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True,
+                  sqrt_mode=None):
+        """`fit` for a table that mixes categorical and real columns (additive; the reference stops at pairwise_cov_matrix,
+        prepare_data.py:253-285, and has no route from it into the model): `dtype` maps column name -> 'c' | 'r'.  The table is encoded
+        on the host (prepare_data.encode_mixed_table), its association matrix -- Cramer's V, the correlation ratio, Pearson's r -- is
+        formed and repaired on the device (uglad_association), and direct-mode training runs on that matrix.  Sets covariance_ (the
+        UNREPAIRED association matrix, float64), precision_, location_ (the means of the 'r' columns, NaN for 'c'), node_names_ (the
+        column names), model_glad, cond_max_ and association_min_eig_; predict(S=...), recovered_graph() and save / load work afterwards.
+        Direct mode only: CV, missing and multitask modes are out of scope for mixed tables -- a fold can lose levels of a categorical,
+        so every fold would need an encoding of its own."""
+        start = time()
+        if verbose:
+            print("Running uGLAD on a mixed table")
+        table, maps = prepare_data.encode_mixed_table(df, dtype)
+        D = table.shape[1]
+        A, mn, A64 = _lib.get_lib().association(torch.from_numpy(table[None]).to(_lib.device()), maps, eval_offset=eval_offset,
+                                                repair=True, want_f64=True)
+        true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
+        with glad.regime_monitor() as regime:
+            pred_theta, compare_theta, model_glad = run_uGLAD_direct(None, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs,
+                                                                     lr=lr, INIT_DIAG=INIT_DIAG, L=L, VERBOSE=verbose,
+                                                                     sqrt_mode=sqrt_mode, Sb=A)
+        self.covariance_ = A64[0].cpu().numpy()
+        self.association_min_eig_ = float(mn[0])
+        self.location_ = np.where(maps.kinds == "r", table.mean(axis=0), np.nan)
+        self.node_names_ = [str(n) for n in maps.names]
+        if pred_theta is not None:
+            self.precision_ = pred_theta[0].detach().cpu().numpy()
+        if model_glad is not None:
+            self.model_glad = model_glad
+        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+        self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit_mixed", None)
         if verbose:
             print(f"Total runtime: {time() - start} secs\n")
         return compare_theta

@@ -4,7 +4,8 @@ This is the one-off O(M*D^2) numpy/pandas work that runs once per ``fit`` before
 unrolled GLAD cell takes over on the device.  Semantics follow the reference
 (``uglad/utils/prepare_data.py``): ``process_table`` :361-516, ``normalize_table``
 :597-613, ``get_covariance`` :328-356, ``convert_to_torch`` :288-307, ``get_data``
-:93-140, ``add_noise_dropout`` :143-169.  Differences, all additive:
+:93-140, ``add_noise_dropout`` :143-169, ``cramers_v`` / ``correlation_ratio`` /
+``pairwise_cov_matrix`` :177-285 (vectorised, no scipy).  Differences, all additive:
 
 * every random draw takes an explicit ``rng`` (``numpy.random.Generator``); the reference
   consumes numpy's and Python's *global* RNG streams, which is why its notebook numbers
@@ -15,7 +16,7 @@ unrolled GLAD cell takes over on the device.  Semantics follow the reference
 from __future__ import annotations
 
 from time import time
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -34,6 +35,12 @@ __all__ = [
     "analyse_condition_number",
     "get_highly_correlated_features",
     "synthetic_covariance_batch",
+    "cramers_v",
+    "correlation_ratio",
+    "pairwise_cov_matrix",
+    "encode_mixed_table",
+    "association_from_codes",
+    "MixedMaps",
 ]
 
 
@@ -241,6 +248,184 @@ def process_table(
     if VERBOSE:
         print(f"{msg}: processed table {table.shape[0]} x {table.shape[1]} in {np.round(time() - start, 3)} s")
     return table
+
+
+# --------------------------------------------------------------------------- mixed tables
+# The association matrix of a table that mixes categorical ('c') and real ('r') columns (ref :177-285): bias-corrected Cramer's V for
+# c/c pairs, the correlation ratio eta for c/r pairs, Pearson's r for r/r pairs.  The reference loops over the D^2 pairs with
+# pd.crosstab / scipy's chi2_contingency / pearsonr; here the table is expanded once -- a 0/1 column per level of every categorical,
+# every real column centred and scaled to unit norm -- and ONE Gram product of the expanded table holds every contingency table, every
+# per-level sum and every Pearson coefficient; a reduction per pair of features finishes it.  The device (csrc/assoc_wide.h) does the
+# same on the expanded layout that encode_mixed_table describes.
+ASSOC_TILE = 64           # a feature's expanded columns never straddle a multiple of this (csrc/chol_wide.h: kT64)
+ASSOC_MAX_DIM = 2048      # uglad_max_dim()
+ASSOC_MAX_WIDTH = 16384   # UGLAD_ASSOC_MAX_WIDTH (include/uglad_hip.h)
+ASSOC_REAL = -1           # the level of a real feature's single expanded column
+ASSOC_PAD = -2            # the level of a padding column (its feature is -1)
+
+
+class MixedMaps(NamedTuple):
+    """The expanded layout of an encoded mixed table (encode_mixed_table): W = len(col_feature) expanded columns, a multiple of 64."""
+    names: list               # the D column names
+    kinds: np.ndarray         # (D,) 'c' | 'r'
+    cards: np.ndarray         # (D,) int32: levels of a categorical, 0 for a real column
+    col_feature: np.ndarray   # (W,) int32: the feature of every expanded column, -1 for padding
+    col_level: np.ndarray     # (W,) int32: its level, ASSOC_REAL for a real column, ASSOC_PAD for padding
+    feat_offset: np.ndarray   # (D,) int32: a feature's first expanded column
+    feat_width: np.ndarray    # (D,) int32: its number of expanded columns (levels, or 1)
+    tile_first: np.ndarray    # (W / 64 + 1,) int32: the first feature of every tile of 64 expanded columns; the last entry is D
+
+    @property
+    def W(self) -> int:
+        return int(self.col_feature.shape[0])
+
+
+def _expanded_layout(names, kinds, cards) -> MixedMaps:
+    D = len(names)
+    width = np.where(kinds == "c", cards, 1).astype(np.int32)
+    offset = np.zeros(D, dtype=np.int32)
+    at = 0
+    for i in range(D):
+        if at % ASSOC_TILE + int(width[i]) > ASSOC_TILE:  # would straddle: start at the next multiple
+            at = (at // ASSOC_TILE + 1) * ASSOC_TILE
+        offset[i] = at
+        at += int(width[i])
+    W = -(-at // ASSOC_TILE) * ASSOC_TILE
+    if W > ASSOC_MAX_WIDTH:
+        raise ValueError(f"the expanded table is {W} columns wide; the limit is {ASSOC_MAX_WIDTH}")
+    col_feature = np.full(W, -1, dtype=np.int32)
+    col_level = np.full(W, ASSOC_PAD, dtype=np.int32)
+    for i in range(D):
+        o, w = int(offset[i]), int(width[i])
+        col_feature[o:o + w] = i
+        col_level[o:o + w] = np.arange(w) if kinds[i] == "c" else ASSOC_REAL
+    tile_first = np.searchsorted(offset, np.arange(0, W + 1, ASSOC_TILE)).astype(np.int32)
+    return MixedMaps(list(names), kinds, cards.astype(np.int32), col_feature, col_level, offset, width, tile_first)
+
+
+def encode_mixed_table(df, dtype):
+    """A table of categorical and real columns -> (table, maps): the float64 (N, D) table whose 'c' columns hold the level codes
+    0 .. card - 1 (pd.factorize order) and whose 'r' columns hold the values, and the MixedMaps of its expanded layout.  `dtype` maps
+    column name -> 'c' | 'r' (ref :253-267).  ValueError, naming the column, for a categorical with more than 64 levels or with missing
+    values, a column with a single value, an unknown type letter; also for more than ASSOC_MAX_DIM columns or an expanded width
+    beyond ASSOC_MAX_WIDTH."""
+    import pandas as pd
+
+    df = pd.DataFrame(df)
+    names = list(df.columns)
+    N, D = df.shape
+    if D > ASSOC_MAX_DIM:
+        raise ValueError(f"{D} columns; the limit is {ASSOC_MAX_DIM}")
+    table = np.empty((N, D), dtype=np.float64)
+    kinds = np.empty(D, dtype="<U1")
+    cards = np.zeros(D, dtype=np.int32)
+    for i, name in enumerate(names):
+        kind = dtype.get(name) if hasattr(dtype, "get") else dtype[name]
+        col = df.iloc[:, i]
+        if kind == "c":
+            if col.isna().any():
+                raise ValueError(f"categorical column {name!r} has missing values")
+            codes, levels = pd.factorize(col)
+            if len(levels) > ASSOC_TILE:
+                raise ValueError(f"categorical column {name!r} has {len(levels)} levels; the limit is {ASSOC_TILE}")
+            if len(levels) < 2:
+                raise ValueError(f"categorical column {name!r} has a single value")
+            table[:, i] = codes
+            cards[i] = len(levels)
+        elif kind == "r":
+            vals = np.asarray(col, dtype=np.float64)
+            seen = vals[~np.isnan(vals)]
+            if seen.size == 0 or seen.min() == seen.max():
+                raise ValueError(f"real column {name!r} has a single value")
+            table[:, i] = vals
+        else:
+            raise ValueError(f"column {name!r} has type {kind!r}; expected 'c' or 'r'")
+        kinds[i] = kind
+    return table, _expanded_layout(names, kinds, cards)
+
+
+def association_from_codes(table, kinds, cards) -> np.ndarray:
+    """The (D, D) float64 association matrix of an encoded table (encode_mixed_table): one-hot Gram, then a reduction per pair.
+    A level without a row in this table is ignored, as pd.crosstab ignores it."""
+    table = np.asarray(table, dtype=np.float64)
+    N, D = table.shape
+    kinds = np.asarray(kinds)
+    cat, real = np.nonzero(kinds == "c")[0], np.nonzero(kinds == "r")[0]
+    A = np.zeros((D, D))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Z = table[:, real]
+        Zc = Z - Z.mean(axis=0)
+        Zn = Zc * (1.0 / np.sqrt((Zc * Zc).sum(axis=0)))  # unit norm: Zn^T Zn is Pearson's r (scipy: dot(xm / |xm|, ym / |ym|))
+        A[np.ix_(real, real)] = Zn.T @ Zn
+        if cat.size == 0:
+            return A
+        width = np.asarray(cards)[cat].astype(np.int64)
+        start = np.concatenate([[0], np.cumsum(width)[:-1]])
+        owner = np.repeat(np.arange(cat.size), width)             # the categorical (its index in `cat`) of every level column
+        level = np.arange(int(width.sum())) - start[owner]
+        H = (table[:, cat[owner]] == level).astype(np.float64)     # (N, levels of all categoricals)
+        cnt = H.sum(axis=0)
+        live = cnt > 0
+        # c/r: eta^2 = sum_a s_a^2 / n_a, s_a the per-level sum of the unit-norm column (= sum_a n_a (mean_a - mean)^2 / sum (y - mean)^2)
+        if real.size:
+            q = np.where(live[:, None], (H.T @ Zn) ** 2 / cnt[:, None], 0.0)
+            eta2 = np.add.reduceat(q, start, axis=0)
+            eta = np.where(eta2 == 0, 0.0, np.sqrt(eta2))
+            A[np.ix_(cat, real)] = eta
+            A[np.ix_(real, cat)] = eta.T
+        # c/c: chi^2 of every contingency table (the Gram blocks), Yates' correction at one degree of freedom, bias-corrected V
+        G = H.T @ H
+        nlive = np.add.reduceat(live.astype(np.int64), start)      # r, k: the levels that occur
+        n = float(N)
+        for a, i in enumerate(cat):
+            rows = slice(start[a], start[a] + width[a])
+            O = G[rows]
+            E = np.outer(cnt[rows], cnt) / n
+            both = live[rows][:, None] & live[None, :]
+            yates = ((nlive[a] - 1) * (nlive - 1) == 1)[owner]
+            diff = E - O
+            O = np.where(yates[None, :], O + np.sign(diff) * np.minimum(0.5, np.abs(diff)), O)
+            chi2 = np.add.reduceat(np.where(both, (O - E) ** 2 / E, 0.0).sum(axis=0), start)
+            r, k = float(nlive[a]), nlive.astype(np.float64)
+            phi2corr = np.maximum(0.0, chi2 / n - (k - 1) * (r - 1) / (n - 1))
+            denom = np.minimum(k - (k - 1) ** 2 / (n - 1) - 1, r - (r - 1) ** 2 / (n - 1) - 1)
+            A[i, cat] = np.where(denom == 0, 0.0, np.sqrt(phi2corr / denom))
+    return A
+
+
+def _encode_pair(x, kx, y, ky):
+    import pandas as pd
+
+    cols, cards = [], []
+    for v, kind in ((x, kx), (y, ky)):
+        if kind == "c":
+            codes, levels = pd.factorize(np.asarray(v))
+            cols.append(codes.astype(np.float64))
+            cards.append(len(levels))
+        else:
+            cols.append(np.asarray(v, dtype=np.float64))
+            cards.append(0)
+    return np.stack(cols, axis=1), np.array([kx, ky]), np.array(cards)
+
+
+def cramers_v(x, y) -> float:
+    """Bias-corrected Cramer's V of two categorical variables, with Yates' correction on a 2 x 2 table as scipy's chi2_contingency
+    applies it (ref :177-209)."""
+    return float(association_from_codes(*_encode_pair(x, "c", y, "c"))[0, 1])
+
+
+def correlation_ratio(categories, measurements) -> float:
+    """The correlation ratio eta of a categorical and a real variable (ref :212-250)."""
+    return float(association_from_codes(*_encode_pair(categories, "c", measurements, "r"))[0, 1])
+
+
+def pairwise_cov_matrix(df, dtype):
+    """The association matrix of a mixed table as a DataFrame indexed by the features (ref :253-285), without the reference's
+    per-row progress lines."""
+    import pandas as pd
+
+    table, maps = encode_mixed_table(df, dtype)
+    return pd.DataFrame(association_from_codes(table, maps.kinds, maps.cards), index=maps.names, columns=maps.names)
 
 
 # --------------------------------------------------------------------------- bench inputs
