@@ -370,6 +370,25 @@ int uglad_conditional_mean_wide(const double* precision, const double* mean, con
                                 double* full_mean, float* cond_cov, double* log_pdf, float* workspace, int K, int D, int clip01,
                                 uglad_stream_t stream);
 
+/* Scoring rows against K fitted models, every 1 <= D <= uglad_max_dim(), fp64 throughout, many workgroups per model (csrc/score_wide.h):
+ * what sklearn's covariance estimators offer as mahalanobis(X) and score_samples(X), which the reference lacks.  With
+ * P = (precision + precision^T) / 2 (formed in fp64) and xc = x - mean:
+ *   mahalanobis (K, N)           q = xc^T P xc, the SQUARED distance (as sklearn returns it); required;
+ *   log_density (K, N) or NULL   (logdet P - D log 2 pi - q) / 2;
+ *   logdet (K) or NULL           from the log-pivots of the blocked Cholesky of uglad_conditional_mean_wide.
+ * X is (x_batch, N, D) with x_batch = K, or 1 for one table scored by every model; precision (K, D, D), mean (K, D); all FP64 DEVICE
+ * pointers.  A row's two numbers depend on that row and the model alone, bit for bit: not on N, on the row's position, on K or on the
+ * model's place in the batch -- so a table may be scored in chunks of rows.  A NaN in a row stays in that row.  P not positive definite (a
+ * pivot <= 0 or NaN): logdet and every log_density of that model are NaN, its mahalanobis values are still returned, the other models are
+ * unaffected.  The factorisation is skipped when log_density and logdet are both NULL.  At most 2 ceil(D / 64) + 4 launches in one chain,
+ * no host readback.  workspace: uglad_sample_scores_workspace_floats(K, N, D) floats (a problem of uglad_conditional_mean_wide per model and
+ * ceil(D / 64) partial sums per model and row), 8-byte aligned (UGLAD_E_NULL otherwise).  K <= 65535, N >= 1, x_batch in {1, K}
+ * (UGLAD_E_DIM otherwise).  Errors as uglad_conditional_mean_wide; the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond
+ * 2^31 - 1 floats, which a large N reaches: score such a table in chunks of rows. */
+int uglad_sample_scores_workspace_floats(int K, int N, int D);
+int uglad_sample_scores(const double* X, int x_batch, const double* precision, const double* mean, double* mahalanobis,
+                        double* log_density, double* logdet, float* workspace, int K, int N, int D, uglad_stream_t stream);
+
 /* After the path.  Partial correlations rho_ij = -p_ij / sqrt(p_ii p_jj) from the upper triangle, mirrored,
  * ones on the diagonal (get_partial_correlations, main.py:796-821), K matrices at once. */
 int uglad_partial_correlations(const float* precision, float* rho, int K, int D, uglad_stream_t stream);

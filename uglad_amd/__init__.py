@@ -28,6 +28,8 @@ from .main import (  # noqa: F401
     conditional_gaussian_batch,
     conditional_gaussian_with_probabilities,
     compute_map_estimate,
+    sample_scores,
+    SampleScores,
     save_uGLAD_model,
     load_uGLAD_model,
 )

@@ -72,6 +72,9 @@ _SIGS = {
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_conditional_mean_wide": ([ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "uglad_sample_scores_workspace_floats": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_sample_scores": ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [_c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                             ctypes.c_void_p], ctypes.c_int),
     "uglad_partial_correlations": ([_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_support_metrics": ([_c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
                               ctypes.c_int),
@@ -416,6 +419,31 @@ class HipLib:
         self._call("uglad_conditional_mean_wide", self._vp(P64), self._vp(mean64), self._p(observed), self._vp(values64), self._vp(full_mean),
                    self._p(cond_cov), self._vp(log_pdf), self._p(wsp), K, D, int(bool(clip01)))
         return full_mean, cond_cov, log_pdf
+
+    def sample_scores(self, X64, P64, mean64, want_density: bool = True):
+        """uglad_sample_scores, every D <= max_dim: X (K,N,D) or (1,N,D) (one table for every model), precision (K,D,D), mean (K,D), all
+        FLOAT64 -> (mahalanobis (K,N): the squared distances xc^T P xc with P the symmetric part of the precision, log_density (K,N),
+        logdet (K)), float64 on the device; the last two are None without `want_density` (the factorisation is skipped).  A model that is
+        not positive definite comes back with NaN in logdet and log_density.  Bit for bit, a row's numbers do not depend on N, on its
+        position, or on K (csrc/score_wide.h)."""
+        what = "sample_scores takes contiguous float64 tensors (K or 1, N, D), (K, D, D), (K, D)"
+        for a, ndim in ((X64, 3), (P64, 3), (mean64, 2)):
+            self._require_f64(a, ndim, what)
+        K, D, _ = P64.shape
+        xb, N, _ = X64.shape
+        if P64.shape[2] != D or X64.shape[2] != D or tuple(mean64.shape) != (K, D) or xb not in (1, K):
+            raise UgladError(what)
+        dev = P64.device
+        n = int(self._dll.uglad_sample_scores_workspace_floats(int(K), int(N), int(D)))
+        if n < 0:
+            self._check("uglad_sample_scores_workspace_floats", n)
+        wsp = torch.empty(n, dtype=torch.float32, device=dev)
+        maha = torch.empty(K, N, dtype=torch.float64, device=dev)
+        dens = torch.empty(K, N, dtype=torch.float64, device=dev) if want_density else None
+        logdet = torch.empty(K, dtype=torch.float64, device=dev) if want_density else None
+        self._call("uglad_sample_scores", self._vp(X64), int(xb), self._vp(P64), self._vp(mean64), self._vp(maha), self._vp(dens),
+                   self._vp(logdet), self._p(wsp), K, N, D)
+        return maha, dens, logdet
 
     def partial_correlations(self, precision):
         K, D, _ = precision.shape

@@ -44,6 +44,7 @@ namespace uglad {
 #include "cov_wide.h"
 #include "assoc_wide.h"
 #include "after_wide.h"
+#include "score_wide.h"
 #include "metrics_wide.h"
 #include "graph_wide.h"
 #endif

@@ -209,6 +209,33 @@ int uglad_conditional_mean_wide(const double* precision, const double* mean, con
   return launch_status();
 }
 
+int uglad_sample_scores_workspace_floats(int K, int N, int D) {
+  if (K < 1 || K > 65535 || N < 1 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  const size_t n = scorew_floats(K, N, D);
+  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
+}
+
+int uglad_sample_scores(const double* X, int x_batch, const double* precision, const double* mean, double* mahalanobis,
+                        double* log_density, double* logdet, float* workspace, int K, int N, int D, uglad_stream_t stream) {
+  if (!X || !precision || !mean || !mahalanobis || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_sample_scores_workspace_floats(K, N, D) < 0 || (x_batch != 1 && x_batch != K)) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const AfterwView v = afterw_view(workspace, D);
+  double* parts = scorew_partials(v, K);
+  const ScorewIn in{X, mean, x_batch, N, D};
+  const int nt = v.c.DP / kT64;
+  const dim3 wg(kWThreads);
+  hipLaunchKernelGGL(scorew_prepare_kernel, dim3(nt, nt, K), wg, 0, st, precision, D, v);
+  hipLaunchKernelGGL(scorew_quad_kernel, dim3((unsigned)((N + (size_t)kT64 - 1) / kT64), nt, K), wg, 0, st, in, v, parts);
+  if (log_density || logdet) {  // the factorisation only for those who read it
+    launch_cholw(st, K, v.c);
+    hipLaunchKernelGGL(scorew_logdet_kernel, dim3(K), wg, 0, st, D, v, logdet);
+  }
+  hipLaunchKernelGGL(scorew_finish_kernel, dim3((unsigned)((N + (size_t)kWThreads - 1) / kWThreads), K), wg, 0, st, N, D, v, parts, mahalanobis,
+                     log_density);
+  return launch_status();
+}
+
 int uglad_partial_correlations(const float* precision, float* rho, int K, int D, uglad_stream_t stream) {
   if (!precision || !rho) return UGLAD_E_NULL;
   if (K < 1 || D < 1) return UGLAD_E_DIM;

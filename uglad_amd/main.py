@@ -16,7 +16,7 @@ from __future__ import annotations
 import contextlib
 import copy
 from time import time
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -638,6 +638,8 @@ class uGLAD_GL(object):
         self.covariance_: Optional[np.ndarray] = None
         self.precision_: Optional[np.ndarray] = None
         self.location_: Optional[np.ndarray] = None
+        self.data_min_: Optional[np.ndarray] = None    # (additive) column minima and ranges of the table fit() normalised: what
+        self.data_range_: Optional[np.ndarray] = None  # places a new row in the model's coordinates (mahalanobis, score_samples, score)
         self.model_glad: Optional[GladParams] = None
         self._fit_cfg = None
 
@@ -647,7 +649,9 @@ class uGLAD_GL(object):
         start = time()
         if verbose:
             print("Running uGLAD")
-        X = np.array(prepare_data.process_table(X, NORM="min_max", VERBOSE=verbose))
+        processed = prepare_data.process_table(X, NORM="min_max", VERBOSE=verbose)
+        data_min, data_range = prepare_data.kept_min_range(X, processed)
+        X = np.array(processed)
         M, D = X.shape
         Xb = X.reshape(1, M, D)
         true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
@@ -665,6 +669,7 @@ class uGLAD_GL(object):
                 raise ValueError(f"Please enter K-fold value in valid range [0, ), currently entered {k_fold}; check mode {mode}")
         self.covariance_ = prepare_data.empirical_covariance(X, assume_centered=centered)
         self.location_ = X.mean(axis=0)
+        self.data_min_, self.data_range_ = data_min, data_range
         self.node_names_ = list(node_names) if node_names is not None else [f"node_{i}" for i in range(D)]
         if pred_theta is not None:
             self.precision_ = pred_theta[0].detach().cpu().numpy()
@@ -702,6 +707,7 @@ class uGLAD_GL(object):
         self.covariance_ = A64[0].cpu().numpy()
         self.association_min_eig_ = float(mn[0])
         self.location_ = np.where(maps.kinds == "r", table.mean(axis=0), np.nan)
+        self.data_min_ = self.data_range_ = None  # (a mixed table is not normalised, and its rows cannot be scored)
         self.node_names_ = [str(n) for n in maps.names]
         if pred_theta is not None:
             self.precision_ = pred_theta[0].detach().cpu().numpy()
@@ -740,6 +746,30 @@ class uGLAD_GL(object):
         return out[0] if out.shape[0] == 1 else out
 
 
+    # ---- scoring rows (additive: sklearn's covariance estimators carry these three, the reference none)
+    def _model_coordinates(self, X, normalized: bool) -> np.ndarray:
+        if self.precision_ is None or self.location_ is None:
+            raise ValueError("call fit() first")
+        if np.isnan(self.location_).any():
+            raise ValueError("location_ holds NaN for the categorical columns of a fit_mixed() table: its rows have no Gaussian score")
+        return _to_model_coordinates(X, None if normalized else (self.data_min_, self.data_range_), len(self.location_))
+
+    def mahalanobis(self, X, normalized: bool = False) -> np.ndarray:
+        """SQUARED Mahalanobis distances (N,) of the rows of X to location_ under precision_ (as sklearn's `mahalanobis`), float64, on
+        the device (uglad_sample_scores).  X has the D columns fit() kept, in node_names_ order, in the units of the training table:
+        it is mapped by (X - data_min_) / data_range_ in fp64 and no row is dropped; `normalized=True` takes X as already mapped.  A
+        NaN in a row gives NaN for that row only."""
+        return sample_scores(self.precision_, self.location_, self._model_coordinates(X, normalized)).mahalanobis
+
+    def score_samples(self, X, normalized: bool = False) -> np.ndarray:
+        """Gaussian log-density (N,) of every row of X under (location_, precision_) (sklearn's `score_samples`); X as for mahalanobis."""
+        return sample_scores(self.precision_, self.location_, self._model_coordinates(X, normalized)).log_density
+
+    def score(self, X, normalized: bool = False) -> float:
+        """The mean of score_samples(X) (sklearn's `score`)."""
+        return float(np.mean(self.score_samples(X, normalized=normalized)))
+
+
 class uGLAD_multitask(object):
     """Drop-in for the reference's `uGLAD_multitask` (main.py:155-226): K tables, one shared model, batched attributes."""
 
@@ -748,6 +778,9 @@ class uGLAD_multitask(object):
         self.device_covariance = bool(device_covariance)
         self.covariance_ = []
         self.precision_: Optional[np.ndarray] = None
+        self.location_: Optional[np.ndarray] = None    # (additive) (K, D) each: the tasks' means, and the column minima and ranges of
+        self.data_min_: Optional[np.ndarray] = None    # the tables fit() normalised (mahalanobis, score_samples, score)
+        self.data_range_: Optional[np.ndarray] = None
         self.model_glad: Optional[GladParams] = None
         self._fit_cfg = None
 
@@ -756,13 +789,17 @@ class uGLAD_multitask(object):
         start = time()
         if verbose:
             print("Running uGLAD in multi-task mode")
-        Xb = [np.array(prepare_data.process_table(X, NORM="min_max", VERBOSE=verbose)) for X in Xb]
+        processed = [prepare_data.process_table(X, NORM="min_max", VERBOSE=verbose) for X in Xb]
+        min_range = [prepare_data.kept_min_range(X, P) for X, P in zip(Xb, processed)]
+        Xb = [np.array(P) for P in processed]
         with device_covariance(self.device_covariance), glad.regime_monitor() as regime:
             pred_theta, compare_theta, model_glad = run_uGLAD_multitask(
                 Xb, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs, lr=lr, INIT_DIAG=INIT_DIAG, L=L,
                 VERBOSE=verbose, sqrt_mode=sqrt_mode)
         self.covariance_ = np.array([prepare_data.empirical_covariance(X, assume_centered=centered) for X in Xb])
         self.precision_ = pred_theta.detach().cpu().numpy()
+        self.location_ = np.array([X.mean(axis=0) for X in Xb])
+        self.data_min_, self.data_range_ = np.array([m for m, _ in min_range]), np.array([r for _, r in min_range])
         self.model_glad = model_glad
         self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
         self.cond_max_ = regime.warn_if_outside("uGLAD_multitask.fit", get_collective())
@@ -789,6 +826,104 @@ class uGLAD_multitask(object):
                               INIT_DIAG=cfg["INIT_DIAG"], sqrt_mode=cfg["sqrt_mode"], collective=Collective())
         self.predict_cond_max_ = regime.warn_if_outside("uGLAD_multitask.predict")
         return theta.cpu().numpy()
+
+
+    # ---- scoring rows (additive, as uGLAD_GL's)
+    def _scores(self, X, normalized: bool):
+        if self.precision_ is None or self.location_ is None:
+            raise ValueError("call fit() first")
+        K, D = self.location_.shape
+        tables = list(X) if isinstance(X, (list, tuple)) or np.ndim(X) == 3 else [X] * K  # K tables pairwise, or one for every task
+        if len(tables) != K:
+            raise ValueError(f"{len(tables)} tables for {K} tasks")
+        mapped = [_to_model_coordinates(T, None if normalized else (self.data_min_[k], self.data_range_[k]), D) for k, T in enumerate(tables)]
+        if len({len(T) for T in mapped}) == 1:
+            return sample_scores(self.precision_, self.location_, np.stack(mapped))
+        each = [sample_scores(self.precision_[k], self.location_[k], T) for k, T in enumerate(mapped)]  # (tables of different lengths)
+        return SampleScores([e.mahalanobis for e in each], [e.log_density for e in each], np.array([e.logdet for e in each]))
+
+    def mahalanobis(self, X, normalized: bool = False):
+        """SQUARED Mahalanobis distances (K, N) of the rows of one (N, D) table to every task's location_ under its precision_, each task
+        mapping X with its own data_min_ / data_range_ (`normalized=True`: X is already mapped); a list of K tables (or a (K, N, D)
+        array) is scored pairwise, table k by task k -- a list of K arrays when their lengths differ.  See uGLAD_GL.mahalanobis."""
+        return self._scores(X, normalized).mahalanobis
+
+    def score_samples(self, X, normalized: bool = False):
+        """Gaussian log-densities (K, N), X as for mahalanobis: for one table the argmax over K is the most likely task of every row."""
+        return self._scores(X, normalized).log_density
+
+    def score(self, X, normalized: bool = False) -> np.ndarray:
+        """(K,) means of score_samples(X) per task."""
+        return np.array([float(np.mean(d)) for d in self._scores(X, normalized).log_density])
+
+
+# ============================================================================================ scoring rows against fitted models
+class SampleScores(NamedTuple):
+    """What sample_scores returns, float64 numpy arrays."""
+    mahalanobis: np.ndarray   # (K, N) squared distances xc^T P xc ((N,) for a single (D, D) model)
+    log_density: np.ndarray   # (K, N) (logdet P - D log 2 pi - q) / 2
+    logdet: np.ndarray        # (K,)   (a float64 scalar for a single model); NaN where P is not positive definite
+
+
+SCORE_ROW_CHUNK = 65536  # rows per call of uglad_sample_scores unless row_chunk says otherwise (halved while the workspace is refused)
+
+
+def _to_model_coordinates(X, min_range, D: int) -> np.ndarray:
+    """(N, D) float64: X as given (min_range None) or mapped by (X - min) / range, the normalisation fit() applied to its own table."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != D:
+        raise ValueError(f"X must be (N, {D}): the columns fit() kept, in node_names_ order; got {X.shape}")
+    if min_range is None:
+        return X
+    mn, rg = min_range
+    if mn is None or rg is None:
+        raise ValueError("this model carries no data_min_ / data_range_ (fitted before they were kept?): pass normalized=True")
+    return (X - mn) / rg
+
+
+def sample_scores(precision, location, X, row_chunk=None) -> SampleScores:
+    """Squared Mahalanobis distance and Gaussian log-density of every row of X under every model, on the device in fp64
+    (uglad_sample_scores, csrc/score_wide.h): precision (D, D) or (K, D, D) -- its symmetric part is used --, location (D,) or (K, D), X
+    (N, D) (one table for every model) or (K, N, D); numpy arrays or device tensors.  Rows go through in chunks of `row_chunk` (default
+    SCORE_ROW_CHUNK, less where the workspace demands it), so any N fits; a row's numbers do not depend on the chunking, bit for bit.  A
+    model that is not positive definite gets NaN in logdet and log_density and keeps its distances; a NaN in a row stays in that row."""
+    lib = _lib.get_lib()
+    dev = _lib.device()
+
+    def to(a):
+        if torch.is_tensor(a):
+            return a.detach().to(device=dev, dtype=torch.float64).contiguous()
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+
+    single = np.ndim(precision) == 2
+    if np.ndim(precision) not in (2, 3) or np.shape(precision)[-1] > lib.max_dim:
+        raise ValueError(f"precision must be (D, D) or (K, D, D) with D <= max_dim = {lib.max_dim}; got {tuple(np.shape(precision))}")
+    P, mu = to(precision), to(location)
+    P = P[None] if P.dim() == 2 else P
+    mu = mu[None] if mu.dim() == 1 else mu
+    if P.dim() != 3 or P.shape[1] != P.shape[2] or tuple(mu.shape) != tuple(P.shape[:2]):
+        raise ValueError(f"precision (K, D, D) and location (K, D); got {tuple(P.shape)} and {tuple(mu.shape)}")
+    K, D = mu.shape
+    if not torch.is_tensor(X):
+        X = np.asarray(X, dtype=np.float64)
+    X = X[None] if X.ndim == 2 else X
+    if X.ndim != 3 or X.shape[2] != D or X.shape[0] not in (1, K) or X.shape[1] < 1:
+        raise ValueError(f"X must be (N, {D}) or ({K}, N, {D}) with N >= 1; got {tuple(X.shape)}")
+    N = X.shape[1]
+    chunk = min(N, int(row_chunk) if row_chunk else SCORE_ROW_CHUNK)
+    if chunk < 1:
+        raise ValueError("row_chunk must be positive")
+    while chunk > 1 and int(lib._dll.uglad_sample_scores_workspace_floats(K, chunk, D)) < 0:
+        chunk = (chunk + 1) // 2
+    maha, dens, logdet = np.empty((K, N)), np.empty((K, N)), None
+    for a in range(0, N, chunk):
+        q, ld, det = lib.sample_scores(to(X[:, a:a + chunk]), P, mu)
+        maha[:, a:a + chunk], dens[:, a:a + chunk] = q.cpu().numpy(), ld.cpu().numpy()
+        logdet = det.cpu().numpy() if logdet is None else logdet  # (the same bits in every chunk)
+    if single:
+        return SampleScores(maha[0], dens[0], logdet[0])
+    return SampleScores(maha, dens, logdet)
 
 
 # ============================================================================================ after the path (SURVEY 8f N3, N4)

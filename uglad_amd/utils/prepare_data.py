@@ -250,6 +250,19 @@ def process_table(
     return table
 
 
+def kept_min_range(raw_table, processed):
+    """Column minima and ranges, (D,) float64 each, of what ``process_table(raw_table, NORM="min_max")`` normalised, over the rows and
+    columns it kept (``processed`` is its return value): ``(raw[kept rows][:, kept columns] - min) / range`` reproduces ``processed`` bit
+    for bit.  The reference throws both away inside its fit; a new row can be placed in the model's coordinates only with them.  (The
+    NaN that process_table fills with the column mean cannot move a minimum or a maximum.)"""
+    import pandas as pd
+
+    raw = pd.DataFrame(raw_table).astype(float)
+    sub = raw.loc[processed.index, processed.columns]
+    mn, mx = sub.min(), sub.max()
+    return mn.to_numpy(dtype=np.float64), (mx - mn).to_numpy(dtype=np.float64)
+
+
 # --------------------------------------------------------------------------- mixed tables
 # The association matrix of a table that mixes categorical ('c') and real ('r') columns (ref :177-285): bias-corrected Cramer's V for
 # c/c pairs, the correlation ratio eta for c/r pairs, Pearson's r for r/r pairs.  The reference loops over the D^2 pairs with
