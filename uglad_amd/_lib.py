@@ -151,9 +151,9 @@ class HipLib:
         if self.require_gpu and not t.is_cuda:
             raise UgladError("uglad_amd kernels take GPU tensors (no CPU fallback)")
 
-    def _wide_workspace(self, name: str, K: int, D: int, device) -> torch.Tensor:
-        """Scratch of <name>_workspace_floats(K, D) floats for one call of the wide entry point `name`; must outlive the enqueue."""
-        n = int(getattr(self._dll, name + "_workspace_floats")(int(K), int(D)))
+    def _wide_workspace(self, name: str, device, *dims: int) -> torch.Tensor:
+        """Scratch of <name>_workspace_floats(*dims) floats for one call of the wide entry point `name`; must outlive the enqueue."""
+        n = int(getattr(self._dll, name + "_workspace_floats")(*map(int, dims)))
         if n < 0:
             self._check(name + "_workspace_floats", n)
         return torch.empty(n, dtype=torch.float32, device=device)
@@ -358,7 +358,7 @@ class HipLib:
         if return_min_eig and not repair:
             raise UgladError("return_min_eig needs repair=True (the eigenvalue comes from the repair's bisection)")
         K, N, D = X64.shape
-        wsp = self._wide_workspace("uglad_covariance_wide", K, D, X64.device)
+        wsp = self._wide_workspace("uglad_covariance_wide", X64.device, K, D)
         S = torch.empty(K, D, D, dtype=torch.float32, device=X64.device)
         mn = torch.empty(K, dtype=torch.float64, device=X64.device) if repair else None
         self._call("uglad_covariance_wide", self._vp(X64), K, N, D, int(bool(normalize)), float(eval_offset), self._p(S), self._vp(mn),
@@ -378,10 +378,7 @@ class HipLib:
         if len(maps.feat_offset) != D:
             raise UgladError(f"association: the maps describe {len(maps.feat_offset)} features, the table has {D}")
         dev = table64.device
-        n = int(self._dll.uglad_association_workspace_floats(K, D, W))
-        if n < 0:
-            self._check("uglad_association_workspace_floats", n)
-        wsp = torch.empty(n, dtype=torch.float32, device=dev)
+        wsp = self._wide_workspace("uglad_association", dev, K, D, W)
         ints = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
                 for a in (maps.col_feature, maps.col_level, maps.feat_offset, maps.feat_width, maps.tile_first)]
         A = torch.empty(K, D, D, dtype=torch.float32, device=dev)
@@ -412,7 +409,7 @@ class HipLib:
         if P64.shape[2] != D or tuple(mean64.shape) != (K, D) or tuple(values64.shape) != (K, D) or tuple(observed.shape) != (K, D):
             raise UgladError("conditional_mean_wide: shapes (K, D, D), (K, D), (K, D), (K, D)")
         dev = P64.device
-        wsp = self._wide_workspace("uglad_conditional_mean_wide", K, D, dev)
+        wsp = self._wide_workspace("uglad_conditional_mean_wide", dev, K, D)
         full_mean = torch.empty(K, D, dtype=torch.float64, device=dev)
         log_pdf = torch.empty(K, dtype=torch.float64, device=dev)
         cond_cov = torch.empty(K, D, D, dtype=torch.float32, device=dev) if want_cov else None
@@ -434,10 +431,7 @@ class HipLib:
         if P64.shape[2] != D or X64.shape[2] != D or tuple(mean64.shape) != (K, D) or xb not in (1, K):
             raise UgladError(what)
         dev = P64.device
-        n = int(self._dll.uglad_sample_scores_workspace_floats(int(K), int(N), int(D)))
-        if n < 0:
-            self._check("uglad_sample_scores_workspace_floats", n)
-        wsp = torch.empty(n, dtype=torch.float32, device=dev)
+        wsp = self._wide_workspace("uglad_sample_scores", dev, K, N, D)
         maha = torch.empty(K, N, dtype=torch.float64, device=dev)
         dens = torch.empty(K, N, dtype=torch.float64, device=dev) if want_density else None
         logdet = torch.empty(K, dtype=torch.float64, device=dev) if want_density else None
@@ -466,7 +460,7 @@ class HipLib:
             raise UgladError("support_metrics_wide: two tensors of shape (K, D, D)")
         K, D, _ = pred_theta.shape
         tp, pp = self._p(true_theta), self._p(pred_theta)
-        wsp = self._wide_workspace("uglad_support_metrics_wide", K, D, pred_theta.device)
+        wsp = self._wide_workspace("uglad_support_metrics_wide", pred_theta.device, K, D)
         out = torch.empty(K, 11, dtype=torch.float64, device=pred_theta.device)
         self._call("uglad_support_metrics_wide", tp, pp, self._vp(out), self._p(wsp), K, D, int(beta))
         return out
@@ -497,7 +491,7 @@ class HipLib:
             if th_in.numel() != K:
                 raise UgladError("graph_wide: one threshold per problem")
             th_in = th_in.to(device=dev, dtype=torch.float32).contiguous()
-        wsp = self._wide_workspace("uglad_graph_wide", K, D, dev)
+        wsp = self._wide_workspace("uglad_graph_wide", dev, K, D)
         i32 = dict(dtype=torch.int32, device=dev)
         out = GraphWide(threshold=torch.empty(K, dtype=torch.float32, device=dev), edge_count=torch.empty(K, **i32),
                         edge_ij=torch.empty(K, E, 2, **i32), edge_w=torch.empty(K, E, dtype=torch.float32, device=dev),

@@ -105,9 +105,8 @@ __global__ __launch_bounds__(kWThreads) void afterw_prepare_kernel(AfterwIn in, 
   double part = 0.0;
   for (int y = w; y < kT64; y += 4)
     if (s_ob[1][y]) part = fma(el(lane, y), s_d[y], part);  // (s_d is 0 in the padding)
-  s_part[w][lane] = part;
-  __syncthreads();
-  if (w == 0) v.rparts(t)[(size_t)J * DP + I * kT64 + lane] = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+  part = t64_sum_waves(part, s_part);
+  if (w == 0) v.rparts(t)[(size_t)J * DP + I * kT64 + lane] = part;
 }
 
 // grid (DP / 64, K), 64 threads
@@ -189,10 +188,8 @@ __global__ __launch_bounds__(kWThreads) void afterw_matvec_kernel(int which, int
       s = fma(m3, x[k + 12], s);
     }
     for (; k < k1; k += 4) s = fma(col[(size_t)k * DP], x[k], s);
-    s_part[w][lane] = s;
-    __syncthreads();
+    const double sum = t64_sum_waves(s, s_part);
     if (w == 0) {
-      const double sum = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
       out[i0 + lane] = which == kAfterwResidual ? v.vec(t, AfterwView::kR)[i0 + lane] - sum : sum;
     }
   }
@@ -242,20 +239,14 @@ __global__ __launch_bounds__(kWThreads) void afterw_finish_kernel(AfterwIn in, i
     full_mean[(size_t)t * D + i] = val;
   }
   if (blockIdx.x != 0 || !log_pdf) return;  // (uniform per workgroup)
-  const double* lp = v.c.log_pivot(t);
-  double s = 0.0;
   int nu = 0;
-  if (ok)
-    for (int k = tid; k < DP; k += kWThreads) s += lp[k];
   for (int k = tid; k < D; k += kWThreads) nu += ob[k] == 0.f;
-  s_sum[tid] = s;
   s_nu[tid] = nu;
-  __syncthreads();
+  const double sum = cholw_log_pivot_sum(v.c, t, DP, ok, s_sum);  // (its barrier publishes s_nu; NaN for a flagged problem)
   if (tid == 0) {
-    double sum = 0.0;
     int n = 0;
-    for (int k = 0; k < kWThreads; ++k) sum += s_sum[k], n += s_nu[k];
-    log_pdf[t] = ok ? fma(-0.5 * (double)n, 1.8378770664093453, 0.5 * sum) : __builtin_nan("");
+    for (int k = 0; k < kWThreads; ++k) n += s_nu[k];
+    log_pdf[t] = fma(-0.5 * (double)n, 1.8378770664093453, 0.5 * sum);
   }
 }
 

@@ -17,10 +17,10 @@
 //                         tile and writes ONE entry of the D x D result into both triangles (the mirror is a copy) of the fp64 slab
 //                         (CholwView::a, row stride DP), the optional fp64 output and the fp32 output
 //   assoc_rowsum_kernel   sum_r |A(r, i)| per column i (= row: A is symmetric to the bit) -> vec3
-//   assoc_control_kernel  covw_control_kernel's sibling: the bracket of an INDEFINITE symmetric matrix, [-||A||_inf, 1e-6] (every
-//                         eigenvalue lies in [-||A||_inf, ||A||_inf]; V and eta are >= 0 while r is signed, so A is far from positive
-//                         semi-definite and cov_wide.h's -2^-30 tr S would not bracket), 48 steps: the bracket ends at ||A||_inf 2^-48
-//   cholw_update_kernel, cholw_panel_kernel<CholwView>, covw_repair_kernel   as in cov_wide.h
+//   the shift bisection of chol_wide.h on AssocBracket (launch_cholw_bisection, as in cov_wide.h): the bracket of an INDEFINITE symmetric
+//                         matrix, [-||A||_inf, 1e-6] (every eigenvalue lies in [-||A||_inf, ||A||_inf]; V and eta are >= 0 while r is
+//                         signed, so A is far from positive semi-definite and cov_wide.h's -2^-30 tr S would not bracket), 48 steps: the
+//                         bracket ends at ||A||_inf 2^-48
 //
 // A thread, not a wave, takes a pair: at the usual cardinalities (2 .. 12) a tile holds hundreds of pairs of a few dozen cells each, and a
 // serial sum per pair has one fixed order.  Every sum has a fixed order; nothing reads back to the host.
@@ -29,7 +29,6 @@
 
 namespace uglad {
 
-constexpr int kAssocSteps = 48;      // bisection steps behind the test at the threshold
 constexpr int kAssocReal = -1;       // col_level of a real feature's column
 constexpr int kAssocPad = -2;        // col_level of a padding column (col_feature -1)
 constexpr int kAssocMaxWidth = 16384;  // W: 256 x 256 tile pairs per table
@@ -68,21 +67,17 @@ __global__ __launch_bounds__(kWThreads) void assoc_stats_kernel(const double* __
       const double x = Xc[(size_t)n * D];
       part += lv >= 0 ? (x == (double)lv ? 1.0 : 0.0) : x;
     }
-  s_p[w][lane] = part;
-  __syncthreads();
-  const double total = ((s_p[0][lane] + s_p[1][lane]) + s_p[2][lane]) + s_p[3][lane];  // (the same bits in the four waves)
+  const double total = t64_sum_waves(part, s_p);
   const double mean = total / (double)N;
-  __syncthreads();
+  __syncthreads();  // (s_p is used again)
   double ss = 0.0;
   if (live && lv == kAssocReal)
     for (int n = w; n < N; n += 4) {
       const double d = Xc[(size_t)n * D] - mean;
       ss += d * d;
     }
-  s_p[w][lane] = ss;
-  __syncthreads();
+  ss = t64_sum_waves(ss, s_p);
   if (w == 0) {
-    ss = ((s_p[0][lane] + s_p[1][lane]) + s_p[2][lane]) + s_p[3][lane];
     double* st = assoc_stats(v, t);
     const bool real = live && lv == kAssocReal;
     st[c] = real ? mean : 0.0;
@@ -208,43 +203,17 @@ __global__ __launch_bounds__(256) void assoc_rowsum_kernel(int D, CholwView v) {
   v.vec3(t)[i] = s;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- bisection control
-// grid (K), one wave; covw_control_kernel with the bracket of an indefinite matrix.  step -1: before the first factorisation (sigma = the
-// threshold); step 0: its result -- positive definite there: no repair, the table leaves; else the bracket [-||A||_inf, threshold];
-// steps 1 .. kAssocSteps: positive definite => lo = sigma, else hi = sigma.
-__global__ __launch_bounds__(64) void assoc_control_kernel(int step, int D, CholwView v) {
-  const int t = blockIdx.x, lane = threadIdx.x;
-  CholwCtl* ctl = v.ctl(t);
-  double nrm = 0.0;
-  if (step == 0) {  // (a maximum: any order gives the same bits)
+// the bisection's bracket: lower end -||A||_inf = -max of the row sums (a maximum: any order gives the same bits)
+struct AssocBracket {
+  static constexpr int kSteps = 48;  // bisection steps behind the test at the threshold
+  __device__ static double lower(const CholwView& v, int t, int D) {
     const double* rs = v.vec3(t);
-    for (int i = lane; i < D; i += 64) nrm = fmax(nrm, rs[i]);
+    double nrm = 0.0;
+    for (int i = (int)threadIdx.x; i < D; i += 64) nrm = fmax(nrm, rs[i]);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) nrm = fmax(nrm, __shfl_xor(nrm, off));
+    return -nrm;
   }
-  if (lane != 0) return;
-  if (step < 0) {
-    ctl->reset(kCovwThreshold);
-    return;
-  }
-  if (!ctl->active) return;
-  const bool pd = ctl->notpd == 0;
-  if (step == 0) {
-    if (pd) {
-      ctl->active = 0;
-      return;
-    }
-    ctl->lo = -nrm;
-    ctl->hi = kCovwThreshold;
-  } else if (pd) {
-    ctl->lo = ctl->sigma;
-  } else {
-    ctl->hi = ctl->sigma;
-  }
-  const double mid = 0.5 * (ctl->lo + ctl->hi);
-  ctl->sigma = mid;
-  ctl->min_eig = mid;  // (after the last step: the estimate)
-  ctl->notpd = 0;
-}
+};
 
 }  // namespace uglad

@@ -1,5 +1,6 @@
-// What the many-workgroup fp64 utilities stand on (cov_wide.h, after_wide.h): the 64 x 64 tile layer on v_mfma_f64_16x16x4_f64 and the
-// blocked Cholesky factorisation of a slab that is spread over many workgroups.
+// What the many-workgroup fp64 utilities stand on (cov_wide.h, assoc_wide.h, after_wide.h, score_wide.h): the 64 x 64 tile layer on
+// v_mfma_f64_16x16x4_f64, the blocked Cholesky factorisation of a slab that is spread over many workgroups, and the bisection of a slab's
+// smallest eigenvalue on that factorisation.
 //
 // The tile layer (t64_): a workgroup of 256 threads owns one 64 x 64 tile; each of its four waves owns a 32 x 32 quadrant as 2 x 2 accumulators
 // f64x4.  The lane-to-element layout of those accumulators is written down ONCE, in t64_for_each_fragment; t64_zero clears them,
@@ -17,6 +18,12 @@
 // CholwInvView the diagonal tile's workgroup also runs the panel's solve on the identity and writes L(j, j)^-T and the 64 log-pivots into
 // slabs of their own behind the control block.  Only a layout that has those slabs can make that view (after_wide.h); a CholwView cannot
 // reach the code that writes them.
+//
+//
+// The shift bisection (cholw_bisect_kernel, cholw_repair_kernel): the reference's repair (prepare_data.py:347-352: where the smallest eigenvalue
+// is <= 1e-6, A += (offset - min eig) I) from factorisations alone.  One at sigma = the threshold takes the reference's decision; for the slabs
+// that fail it, Bracket::kSteps bisection steps on [Bracket::lower, threshold] bracket the smallest eigenvalue.  The client owns the Bracket
+// (where its matrix's smallest eigenvalue cannot lie below, and how many steps that bracket needs); the controller and the repair are here.
 //
 // Every sum has a fixed order (the k-ordered fma chain of the MFMA, columns in index order), so results are bit-reproducible.
 #pragma once
@@ -55,6 +62,14 @@ __device__ __forceinline__ void t64_zero(f64x4 (&acc)[2][2]) {
 template <class F>
 __device__ __forceinline__ void t64_for_each_element(F&& f) {
   for (int idx = threadIdx.x; idx < kT64 * kT64; idx += kWThreads) f(idx >> 6, idx & 63);
+}
+// thread = element (lane) x group (wave) of a 64-wide row: the four waves' partial sums of element `lane`, combined in wave order -- the same
+// bits in the four waves.  One barrier, behind the stores; a caller that uses s_part again puts its own barrier in front of that.
+__device__ __forceinline__ double t64_sum_waves(double part, double (&s_part)[4][kT64]) {
+  const int lane = threadIdx.x & 63;
+  s_part[threadIdx.x >> 6][lane] = part;
+  __syncthreads();
+  return ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the tile product
@@ -114,7 +129,7 @@ __device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, do
 }
 
 // ---------------------------------------------------------------------------------------------------------------- control block and views
-// One per slab (8 doubles of the workspace).  The factorisation reads sigma, notpd and active; the rest is the covariance's bisection.
+// One per slab (8 doubles of the workspace).  The factorisation reads sigma, notpd and active; the rest is the bisection's (below).
 struct CholwCtl {
   double lo, hi;   // (bisection) the bracket of the smallest eigenvalue
   double sigma;    // the shift of the factorisation under way
@@ -169,6 +184,21 @@ __device__ __forceinline__ bool cholw_gate(const CholwCtl* ctl) {
   if (threadIdx.x == 0) s_go = ctl->active != 0 && ctl->notpd == 0;
   __syncthreads();
   return s_go != 0;
+}
+
+// log det of a factored slab = the sum of its first n log-pivots: 256 strided partial sums, combined by thread 0 in thread order (valid in
+// thread 0 alone); NaN for a slab whose factorisation broke down (ok = cholw_gate's answer).  One barrier, behind the stores into s_sum.
+__device__ __forceinline__ double cholw_log_pivot_sum(const CholwInvView& v, int t, int n, bool ok, double (&s_sum)[kWThreads]) {
+  const double* lp = v.log_pivot(t);
+  double s = 0.0;
+  if (ok)
+    for (int k = threadIdx.x; k < n; k += kWThreads) s += lp[k];
+  s_sum[threadIdx.x] = s;
+  __syncthreads();
+  double sum = 0.0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < kWThreads; ++k) sum += s_sum[k];
+  return ok ? sum : __builtin_nan("");
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Cholesky, launch A
@@ -256,6 +286,66 @@ __global__ __launch_bounds__(kWThreads) void cholw_panel_kernel(int j, View v) {
     }
   }
   t64_for_each_element([&](int rr, int cc) { L[(size_t)(i0 + rr) * DP + j0 + cc] = s_t[rr * kT64Ldt + cc]; });
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the shift bisection
+constexpr double kCholwThreshold = 1e-6;  // prepare_data.py:347
+
+// grid (K), one wave, between two factorisations: reads the "not PD" flag, moves the bracket, chooses the next sigma.  step -1: before the
+// first factorisation (sigma = the threshold); step 0: its result -- positive definite there: no repair, the slab leaves; else the bracket
+// [Bracket::lower, threshold]; steps 1 .. Bracket::kSteps: positive definite => lo = sigma, else hi = sigma.
+// Bracket (the client's): static constexpr int kSteps; __device__ static double lower(const CholwView&, int t, int D), called by the whole
+// wave, every sum in it in a fixed order.
+template <class Bracket>
+__global__ __launch_bounds__(64) void cholw_bisect_kernel(int step, int D, CholwView v) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  CholwCtl* ctl = v.ctl(t);
+  double lower = 0.0;
+  if (step == 0) lower = Bracket::lower(v, t, D);
+  if (lane != 0) return;
+  if (step < 0) {
+    ctl->reset(kCholwThreshold);
+    return;
+  }
+  if (!ctl->active) return;
+  const bool pd = ctl->notpd == 0;
+  if (step == 0) {
+    if (pd) {
+      ctl->active = 0;
+      return;
+    }
+    ctl->lo = lower;
+    ctl->hi = kCholwThreshold;
+  } else if (pd) {
+    ctl->lo = ctl->sigma;
+  } else {
+    ctl->hi = ctl->sigma;
+  }
+  const double mid = 0.5 * (ctl->lo + ctl->hi);
+  ctl->sigma = mid;
+  ctl->min_eig = mid;  // (after the last step: the estimate)
+  ctl->notpd = 0;
+}
+
+// The bisection's last step.  grid (ceil(D / 256), K): A += (eval_offset - min eig) I for the slabs that failed the test at the threshold, the
+// diagonal of the fp32 output rewritten from it (one rounding); min_eig_out[t] = the smallest eigenvalue before the repair, or +infinity for
+// a slab that passed (its eigenvalue is never computed)
+__global__ __launch_bounds__(256) void cholw_repair_kernel(int D, double eval_offset, CholwView v, float* __restrict__ A_out,
+                                                           double* __restrict__ min_eig_out) {
+  const int t = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  CholwCtl* ctl = v.ctl(t);
+  const bool active = ctl->active != 0;
+  const double mn = ctl->min_eig;
+  if (active && i < D) {
+    double* A = v.a(t);
+    const double d = A[(size_t)i * v.DP + i] + (eval_offset - mn);
+    A[(size_t)i * v.DP + i] = d;
+    A_out[(size_t)t * D * D + (size_t)i * D + i] = (float)d;
+  }
+  if (i == 0) {
+    min_eig_out[t] = active ? mn : __builtin_inf();
+    ctl->repaired = active ? 1 : 0;
+  }
 }
 
 }  // namespace uglad

@@ -4,20 +4,20 @@
 // smallest eigenvalue is <= 1e-6, S += (offset - min eig) I) needs no eigensolver at all:
 //
 //   S - sigma I is positive definite  <=>  min eig > sigma,  and a Cholesky factorisation that completes or breaks down decides the left
-//   side backward-stably (chol_wide.h, which holds the factorisation and its error bound).  One factorisation at sigma = 1e-6 takes the reference's
-//   decision; for the tables that fail it, 24 bisection steps on [-2^-30 tr S, 1e-6] (S is a Gram matrix: min eig >= -O(1e-16) tr) bracket
-//   the smallest eigenvalue to (1e-6 + 2^-30 tr) / 2^24.  An fp32 inertia count cannot do this: its error ~ sqrt(D) 6e-8 ||S|| is far above
-//   the threshold, and a rank-deficient table (N < D, the normal case at these sizes) has min eig ~ 0.
+//   side backward-stably (chol_wide.h, which holds the factorisation, its error bound and the bisection on it).  One factorisation at
+//   sigma = 1e-6 takes the reference's decision; for the tables that fail it, 24 bisection steps on [-2^-30 tr S, 1e-6] (CovwBracket; S is a
+//   Gram matrix: min eig >= -O(1e-16) tr) bracket the smallest eigenvalue to (1e-6 + 2^-30 tr) / 2^24.  An fp32 inertia count cannot do
+//   this: its error ~ sqrt(D) 6e-8 ||S|| is far above the threshold, and a rank-deficient table (N < D, the normal case at these sizes) has
+//   min eig ~ 0.
 //
 //   covw_stats_kernel     per table and block of 64 columns: min, max, mean -> mn, scale, mu (fp64; the semantics of cov_kernel)
 //   covw_gram_kernel      one workgroup per upper 64 x 64 tile: S = Xc^T Xc / N on the fp64 MFMA, the table streaming through LDS centred
 //                         and normalised; writes the fp64 slab S64 (row stride DP = D rounded up to 64, identity in the padding) and the
 //                         fp32 S_out, both triangles (the mirror is a copy: exactly symmetric)
-//   covw_control_kernel   one workgroup of one wave per table, between two factorisations: reads the "not PD" flag, moves the bracket,
-//                         chooses the next sigma
-//   cholw_update_kernel, cholw_panel_kernel<CholwView>
-//                         the blocked Cholesky of S64 - sigma I into the slab W, two launches per block column of 64 (chol_wide.h)
-//   covw_repair_kernel    active tables: the diagonal of S64 += offset - min eig, the diagonal of S_out rewritten from it (one rounding)
+//   25 x { cholw_bisect_kernel<CovwBracket>, cholw_update_kernel + cholw_panel_kernel<CholwView> per block column of 64 },
+//   cholw_bisect_kernel<CovwBracket>, cholw_repair_kernel
+//                         the shift bisection of chol_wide.h (launch_cholw_bisection): the test at the threshold and 24 steps, each a
+//                         blocked Cholesky of S64 - sigma I into the slab W; then the diagonals of S64 and S_out += offset - min eig
 //
 // Every sum has a fixed order (rows over waves combined in wave order, the k-ordered fma chain of the MFMA), so results are bit-reproducible.
 // Nothing reads back to the host: the whole sequence (2 + 1 + 25 (2 DP / 64 + 1) + 1 launches) can be captured into a graph.
@@ -25,9 +25,6 @@
 #include "chol_wide.h"
 
 namespace uglad {
-
-constexpr int kCovwSteps = 24;    // bisection steps behind the test at the threshold
-constexpr double kCovwThreshold = 1e-6;  // prepare_data.py:347
 
 // A table's part of the workspace, in DOUBLES (the buffer is 8-byte aligned; DP = D rounded up to 64), is the factorisation's slab and no more:
 //   S64   DP x DP   the covariance in fp64, row stride DP, identity in the padding; repaired in place (CholwView::a)
@@ -40,6 +37,18 @@ __host__ inline CholwView covw_view(float* workspace, int D) {
   return CholwView{reinterpret_cast<double*>(workspace), covw_table_doubles(DP), DP};
 }
 __host__ inline size_t covw_table_floats(int D) { return 2 * covw_table_doubles(t64_padded(D)); }
+
+// the bisection's bracket of a Gram matrix: lower end -2^-30 tr S (the trace of the D x D matrix, lanes striding the diagonal, combined in a
+// fixed order)
+struct CovwBracket {
+  static constexpr int kSteps = 24;  // bisection steps behind the test at the threshold
+  __device__ static double lower(const CholwView& v, int t, int D) {
+    const double* S64 = v.a(t);
+    double tr = 0.0;
+    for (int i = (int)threadIdx.x; i < D; i += 64) tr += S64[(size_t)i * v.DP + i];
+    return -wave_sum_f64(tr) * (1.0 / 1073741824.0);
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- column statistics
 // grid (DP / 64, K): thread = column (lane) x row group (wave); rows w, w + 4, ...; the four partial results combined in wave order
@@ -118,64 +127,6 @@ __global__ __launch_bounds__(kWThreads) void covw_gram_kernel(const double* __re
       if (i != j) So[(size_t)j * D + i] = (float)val;
     }
   });
-}
-
-// ---------------------------------------------------------------------------------------------------------------- bisection control
-// grid (K), one wave.  step -1: before the first factorisation (sigma = the threshold); step 0: its result -- positive definite there: no
-// repair, the table leaves; else the bracket [-2^-30 tr S, threshold]; steps 1 .. kCovwSteps: positive definite => lo = sigma, else hi = sigma.
-__global__ __launch_bounds__(64) void covw_control_kernel(int step, int D, CholwView v) {
-  const int t = blockIdx.x, lane = threadIdx.x;
-  CholwCtl* ctl = v.ctl(t);
-  double tr = 0.0;
-  if (step == 0) {  // (the trace of the D x D matrix, lanes striding the diagonal, combined in a fixed order)
-    const double* S64 = v.a(t);
-    for (int i = lane; i < D; i += 64) tr += S64[(size_t)i * v.DP + i];
-    tr = wave_sum_f64(tr);
-  }
-  if (lane != 0) return;
-  if (step < 0) {
-    ctl->reset(kCovwThreshold);
-    return;
-  }
-  if (!ctl->active) return;
-  const bool pd = ctl->notpd == 0;
-  if (step == 0) {
-    if (pd) {
-      ctl->active = 0;
-      return;
-    }
-    ctl->lo = -tr * (1.0 / 1073741824.0);
-    ctl->hi = kCovwThreshold;
-  } else if (pd) {
-    ctl->lo = ctl->sigma;
-  } else {
-    ctl->hi = ctl->sigma;
-  }
-  const double mid = 0.5 * (ctl->lo + ctl->hi);
-  ctl->sigma = mid;
-  ctl->min_eig = mid;  // (after the last step: the estimate)
-  ctl->notpd = 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- repair
-// grid (ceil(D / 256), K): S += (eval_offset - min eig) I for the tables that failed the test at the threshold; min_eig_out[t] = the
-// smallest eigenvalue before the repair, or +infinity for a table that passed (its eigenvalue is never computed)
-__global__ __launch_bounds__(256) void covw_repair_kernel(int D, double eval_offset, CholwView v, float* __restrict__ S_out,
-                                                          double* __restrict__ min_eig_out) {
-  const int t = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  CholwCtl* ctl = v.ctl(t);
-  const bool active = ctl->active != 0;
-  const double mn = ctl->min_eig;
-  if (active && i < D) {
-    double* S64 = v.a(t);
-    const double d = S64[(size_t)i * v.DP + i] + (eval_offset - mn);
-    S64[(size_t)i * v.DP + i] = d;
-    S_out[(size_t)t * D * D + (size_t)i * D + i] = (float)d;
-  }
-  if (i == 0) {
-    min_eig_out[t] = active ? mn : __builtin_inf();
-    ctl->repaired = active ? 1 : 0;
-  }
 }
 
 }  // namespace uglad

@@ -45,6 +45,7 @@ namespace uglad {
 #include "assoc_wide.h"
 #include "after_wide.h"
 #include "score_wide.h"
+#include "sort_wide.h"
 #include "metrics_wide.h"
 #include "graph_wide.h"
 #endif
@@ -119,4 +120,5 @@ UGLAD_KERNELS_NT_GE5(UGLAD_DECLARE, 5) UGLAD_KERNELS_NT_GE5(UGLAD_DECLARE, 6) UG
 #include "host_api.h"
 #include "host_rccl.h"
 #include "host_extra.h"
+#include "host_wide.h"
 #endif  // !UGLAD_TU_NT

@@ -8,9 +8,9 @@
 //   edge (i, j) is kept iff rho_ij > th or rho_ij < -th (floats, both strict: a NaN threshold keeps nothing, a NaN rho is no edge)
 //   A = the 0/1 adjacency, d_i its row sums, t_i = sum_j A_ij (A A)_ij = twice the triangles at node i
 //
-//   gw_keys_kernel       one workgroup per 64 x 64 tile of the upper triangle, as mw_keys_kernel: the key bits(rho) & 0x7fffffff at the edge's
+//   gw_keys_kernel       one workgroup per 64 x 64 tile of the upper triangle, as metrics_wide.h's mw_keys_kernel: the key bits(rho) & 0x7fffffff at the edge's
 //                        row-major index (|NaN| sorts last, as numpy sorts it)
-//   8 x { mw_hist_kernel, mw_scan_kernel, mw_scatter_kernel }     the radix sort of metrics_wide.h as it is, on an MwView of this workspace
+//   8 x { sortw_hist_kernel, sortw_scan_kernel, sortw_scatter_kernel }     the radix sort of sort_wide.h (launch_sortw)
 //   gw_threshold_kernel  one thread per problem: th from the sorted keys, or the given one (n_keep = -1)
 //   gw_row_kernel        one workgroup per row of the padded plane: membership from the symmetric read [min(i, j)][max(i, j)] (A is exactly
 //                        symmetric), row i of A as fp32 0/1 (leading dimension and row count padded to 64, zero-filled), d_i, the kept j > i
@@ -29,42 +29,45 @@
 // No atomics, no ballot, every sum in a fixed order, every buffer belongs to one problem: results are bit-reproducible and independent of K and
 // of the problem's place in the batch.  One linear chain of launches, no host readback.
 #pragma once
-#include "metrics_wide.h"
+#include "sort_wide.h"
 
 namespace uglad {
 
+constexpr int kGwTile = kWT;    // tile of the plane: of the keys, the counts and the triangle product
 constexpr int kGwKeepPer = 64;  // problems per launch of gw_threshold_kernel: their n_keep travel by value
 struct GwKeep {
   int n[kGwKeepPer];
 };
 
 // One problem's part of the workspace in 4-byte words, every part even:
-//   keys 0 | keys 1 | hist     the sort's part of an MwView (metrics_wide.h)
+//   keys 0 | keys 1 | hist     the sort's part (SortwView, sort_wide.h)
 //   th       2                 the threshold (float), m (int)
 //   upper    DP                kept j > i of row i, then their exclusive scan
 //   tile     nt x nt           edges in the 64 x 64 tile of A
 //   rowtile  DP x nt           edges of row i in column block J
 //   tpart    DP x nt           row i's part of t_i from tile column J
 //   adj      DP x DP           A, fp32 0/1
+__host__ __device__ constexpr size_t gw_tile_words(size_t nt) { return (nt * nt + 1) & ~(size_t)1; }
+__host__ __device__ constexpr size_t gw_problem_words(size_t E, size_t tiles, size_t nt, size_t DP) {
+  return sortw_words(E, tiles) + 2 + DP + gw_tile_words(nt) + 2 * DP * nt + DP * DP;
+}
 struct GwView {
-  MwView s;
-  int D, DP;
-  __host__ __device__ size_t tile_words() const { return ((size_t)s.nt * s.nt + 1) & ~(size_t)1; }
-  __host__ __device__ int* base(int k) const { return s.hist(k) + (size_t)kMwBins * s.tiles; }
+  SortwView s;
+  int nt, D, DP;
+  __host__ __device__ size_t tile_words() const { return gw_tile_words((size_t)nt); }
+  __host__ __device__ int* base(int k) const { return s.behind(k); }
   __host__ __device__ float* th(int k) const { return reinterpret_cast<float*>(base(k)); }
   __host__ __device__ int* upper(int k) const { return base(k) + 2; }
   __host__ __device__ int* tile(int k) const { return upper(k) + DP; }
   __host__ __device__ int* rowtile(int k) const { return tile(k) + tile_words(); }
-  __host__ __device__ int* tpart(int k) const { return rowtile(k) + (size_t)DP * s.nt; }
-  __host__ __device__ float* adj(int k) const { return reinterpret_cast<float*>(tpart(k) + (size_t)DP * s.nt); }
+  __host__ __device__ int* tpart(int k) const { return rowtile(k) + (size_t)DP * nt; }
+  __host__ __device__ float* adj(int k) const { return reinterpret_cast<float*>(tpart(k) + (size_t)DP * nt); }
 };
 __host__ inline GwView gw_view(float* workspace, int D) {
-  MwView s = mw_view(workspace, D);
-  GwView v{s, D, s.nt * kMwKeyTile};
-  v.s.pair = 2 * s.epad() + (size_t)kMwBins * s.tiles + 2 + v.DP + v.tile_words() + 2 * (size_t)v.DP * s.nt + (size_t)v.DP * v.DP;
-  return v;
+  const int E = D * (D - 1) / 2, tiles = sortw_tiles(E), nt = (D + kGwTile - 1) / kGwTile, DP = nt * kGwTile;
+  return GwView{SortwView{reinterpret_cast<unsigned*>(workspace), gw_problem_words((size_t)E, (size_t)tiles, (size_t)nt, (size_t)DP), E, tiles}, nt, D, DP};
 }
-__host__ inline size_t gw_problem_floats(int D) { return gw_view(nullptr, D).s.pair; }
+__host__ inline size_t gw_problem_floats(int D) { return gw_view(nullptr, D).s.stride; }
 
 // the value of edge (i, j), i < j
 __device__ __forceinline__ float gw_rho(const float* __restrict__ Vm, int D, int i, int j, int from_precision) {
@@ -80,9 +83,9 @@ __global__ __launch_bounds__(kWThreads) void gw_keys_kernel(const float* __restr
   if (I > J) return;  // (uniform per workgroup)
   const float* Vm = values + (size_t)k * D * D;
   unsigned* keys = v.s.keys(k, 0);
-  const int j = J * kMwKeyTile + (tid & 63);
-  for (int r = tid >> 6; r < kMwKeyTile; r += 4) {
-    const int i = I * kMwKeyTile + r;
+  const int j = J * kGwTile + (tid & 63);
+  for (int r = tid >> 6; r < kGwTile; r += 4) {
+    const int i = I * kGwTile + r;
     if (i < j && j < D) keys[i * D - (i * (i + 1)) / 2 + (j - i - 1)] = (unsigned)__float_as_int(gw_rho(Vm, D, i, j, from_precision)) & 0x7fffffffu;
   }
 }
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(kWThreads) void gw_row_kernel(const float* __restri
   const int i = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, D = v.D, DP = v.DP;
   const float* Vm = values + (size_t)k * D * D;
   float* arow = v.adj(k) + (size_t)i * DP;
-  int* rt = v.rowtile(k) + (size_t)i * v.s.nt;
+  int* rt = v.rowtile(k) + (size_t)i * v.nt;
   const float th = v.th(k)[0];
   int deg = 0, up = 0;
   for (int j0 = 0; j0 < DP; j0 += kWThreads) {
@@ -123,8 +126,8 @@ __global__ __launch_bounds__(kWThreads) void gw_row_kernel(const float* __restri
     deg += e;
     up += (e && j > i) ? 1 : 0;
   }
-  deg = mw_block_sum(deg, s_w);
-  up = mw_block_sum(up, s_w);
+  deg = sortw_block_sum(deg, s_w);
+  up = sortw_block_sum(up, s_w);
   if (tid == 0) {
     v.upper(k)[i] = up;
     if (i < D) degree[(size_t)k * D + i] = deg;
@@ -134,13 +137,13 @@ __global__ __launch_bounds__(kWThreads) void gw_row_kernel(const float* __restri
 // grid (K): upper -> its exclusive scan over the rows (where row i's edges start), m; the tile counts
 __global__ __launch_bounds__(kWThreads) void gw_scan_kernel(int* __restrict__ edge_count, GwView v) {
   __shared__ int s_w[4];
-  const int k = blockIdx.x, tid = threadIdx.x, nt = v.s.nt;
+  const int k = blockIdx.x, tid = threadIdx.x, nt = v.nt;
   int* h = v.upper(k);
   const int n = v.DP, per = (n + kWThreads - 1) / kWThreads;
   const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
   int s = 0;
   for (int q = lo; q < hi; ++q) s += h[q];
-  int run = mw_block_scan<false>(s, s_w);
+  int run = sortw_block_scan<false>(s, s_w);
   for (int q = lo; q < hi; ++q) {
     const int c = h[q];
     h[q] = run;
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(kWThreads) void gw_scan_kernel(int* __restrict__ ed
   for (int t = tid; t < nt * nt; t += kWThreads) {
     const int I = t / nt, J = t - I * nt;
     int c = 0;
-    for (int r = 0; r < kMwKeyTile; ++r) c += rt[(size_t)(I * kMwKeyTile + r) * nt + J];
+    for (int r = 0; r < kGwTile; ++r) c += rt[(size_t)(I * kGwTile + r) * nt + J];
     tc[t] = c;
   }
 }
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(kWThreads) void gw_edges_kernel(const float* __rest
   for (int j0 = i + 1; j0 < D; j0 += kWThreads) {  // (uniform per workgroup)
     const int j = j0 + tid;
     const int e = (j < D && arow[j] != 0.f) ? 1 : 0;
-    const int before = mw_block_scan<false>(e, s_w);
+    const int before = sortw_block_scan<false>(e, s_w);
     const int total = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);  // (the waves' totals, left by the scan; its next call starts with a barrier)
     if (e) {
       const size_t at = (size_t)k * v.s.E + (size_t)(run + before);
@@ -188,9 +191,9 @@ __global__ __launch_bounds__(kWThreads) void gw_edges_kernel(const float* __rest
 // grid (nt, nt, K): tile (I, J) = (blockIdx.y, blockIdx.x) of (A A) o A -> tpart[row][J] for the 64 rows of I
 __global__ __launch_bounds__(kWThreads) void gw_triangles_kernel(GwView v) {
   __shared__ float sA[kWK * kWLd], sB[kWK * kWLd];
-  static_assert(kWK == kMwKeyTile && kWT == kMwKeyTile, "one tile size for the plane, the counts and the product");
+  static_assert(kWK == kGwTile, "one tile size for the plane, the counts and the product");
   const int I = blockIdx.y, J = blockIdx.x, k = blockIdx.z, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nt = v.s.nt, DP = v.DP;
+  const int nt = v.nt, DP = v.DP;
   const int* tc = v.tile(k);
   int* part = v.tpart(k) + (size_t)(I * kWT) * nt + J;
   if (tc[I * nt + J] == 0) {  // (uniform per workgroup) the mask is zero
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(kWThreads) void gw_triangles_kernel(GwView v) {
 
 // grid (ceil(D / 256), K)
 __global__ __launch_bounds__(kWThreads) void gw_rowsum_kernel(int* __restrict__ triangles2, GwView v) {
-  const int i = blockIdx.x * kWThreads + threadIdx.x, k = blockIdx.y, nt = v.s.nt;
+  const int i = blockIdx.x * kWThreads + threadIdx.x, k = blockIdx.y, nt = v.nt;
   if (i >= v.D) return;
   const int* part = v.tpart(k) + (size_t)i * nt;
   int t = 0;

@@ -1,27 +1,8 @@
-// Host layer, part 5: the utilities around the pass (consensus, symeig, covariance, conditional mean, metrics) and the diagnostic exports of
-// the development builds (UGLAD_PHASE_EXIT, UGLAD_STAMPS).
+// Host layer, part 5: the one-workgroup utilities around the pass (consensus, symeig, covariance, conditional mean, metrics) and the diagnostic
+// exports of the development builds (UGLAD_PHASE_EXIT, UGLAD_STAMPS).  Their many-workgroup counterparts are in host_wide.h.
 #pragma once
 // the route of a utility: its batch is one group, and only the tridiagonalisation flavour is asked of it
 static Route util_route(int M, int D) { return make_route(M, D, 1, false, UGLAD_SQRT_EXACT); }
-
-// ---- the many-workgroup fp64 utilities (chol_wide.h and its clients, metrics_wide.h).  Their workspaces are described once, by the view in the
-// kernel header and its factory; here are the checks and the launches they share.
-// *_workspace_floats: K items of floats_per_item(D) floats, for min_D <= D <= UGLAD_MAX_DIM; a size beyond 2^31 - 1 is refused like a dimension
-static int wide_workspace_floats(int K, int D, int min_D, size_t (*floats_per_item)(int D)) {
-  if (K < 1 || K > 65535 || D < min_D || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const size_t n = (size_t)K * floats_per_item(D);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
-static bool wide_workspace_ok(const float* workspace) { return workspace && !(reinterpret_cast<size_t>(workspace) & 7); }
-// the blocked Cholesky of K slabs: update + panel for every block column; a CholwInvView also gets L(j, j)^-T and the log-pivots
-template <class View>
-static void launch_cholw(hipStream_t st, int K, const View& v) {
-  const int nt = v.DP / kT64;
-  for (int j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(cholw_update_kernel, dim3(nt - j, K), dim3(kWThreads), 0, st, j, static_cast<const CholwView&>(v));
-    hipLaunchKernelGGL(cholw_panel_kernel<View>, dim3(nt - j, K), dim3(kWThreads), 0, st, j, v);
-  }
-}
 
 extern "C" {
 
@@ -70,62 +51,6 @@ int uglad_covariance(const float* X, int K, int N, int D, int normalize, float e
   float* beta = eig_scratch + (size_t)K * D * D;
   if ((rc = uglad_symeig(S_out, eig_scratch, beta, workspace, K, D, stream))) return rc;
   hipLaunchKernelGGL(cov_repair_kernel, dim3(K), dim3(256), 0, st, S_out, beta, D, eval_offset);
-  return launch_status();
-}
-
-int uglad_covariance_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, covw_table_floats); }
-
-int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, double eval_offset, float* S_out, double* min_eig_out,
-                          float* workspace, uglad_stream_t stream) {
-  if (!X || !S_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
-  if (uglad_covariance_wide_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
-  if (normalize != 0 && normalize != 1) return UGLAD_E_MODE;
-  hipStream_t st = (hipStream_t)stream;
-  const CholwView v = covw_view(workspace, D);
-  const int nt = v.DP / kT64;
-  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X, N, D, normalize, v);
-  hipLaunchKernelGGL(covw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, v, S_out);
-  if (!min_eig_out) return launch_status();  // no repair
-  // the test at the threshold, then the bisection: tables that are done (or whose factorisation has broken down) cost empty launches
-  for (int step = 0; step <= kCovwSteps; ++step) {
-    hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, v);
-    launch_cholw(st, K, v);
-  }
-  hipLaunchKernelGGL(covw_control_kernel, dim3(K), dim3(64), 0, st, kCovwSteps, D, v);
-  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, v, S_out, min_eig_out);
-  return launch_status();
-}
-
-int uglad_association_max_width(void) { return UGLAD_ASSOC_MAX_WIDTH; }
-static_assert(UGLAD_ASSOC_MAX_WIDTH == kAssocMaxWidth, "the header's constant is the kernels'");
-
-int uglad_association_workspace_floats(int K, int D, int W) {
-  if (K < 1 || K > 65535 || D < 2 || D > UGLAD_MAX_DIM || W < D || W > kAssocMaxWidth || W % kT64) return UGLAD_E_DIM;
-  const size_t n = (size_t)K * 2 * assoc_table_doubles(t64_padded(D), W);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
-
-int uglad_association(const double* table, int K, int N, int D, const int* col_feature, const int* col_level, const int* feat_offset,
-                      const int* feat_width, const int* tile_first, int W, double eval_offset, float* A_out, double* A64_out,
-                      double* min_eig_out, float* workspace, uglad_stream_t stream) {
-  if (!table || !col_feature || !col_level || !feat_offset || !feat_width || !tile_first || !A_out || !wide_workspace_ok(workspace))
-    return UGLAD_E_NULL;
-  if (uglad_association_workspace_floats(K, D, W) < 0 || N < 2) return UGLAD_E_DIM;  // (N = 1: the bias correction divides by N - 1)
-  hipStream_t st = (hipStream_t)stream;
-  const CholwView v = assoc_view(workspace, D, W);
-  const AssocMaps m{col_feature, col_level, feat_offset, feat_width, tile_first, W};
-  const int wt = W / kT64;
-  hipLaunchKernelGGL(assoc_stats_kernel, dim3(wt, K), dim3(kWThreads), 0, st, table, N, D, m, v);
-  hipLaunchKernelGGL(assoc_gram_kernel, dim3(wt, wt, K), dim3(kWThreads), 0, st, table, N, D, m, v, A64_out, A_out);
-  if (!min_eig_out) return launch_status();  // no repair
-  // as uglad_covariance_wide: the test at the threshold, then the bisection -- on the bracket of an indefinite matrix
-  hipLaunchKernelGGL(assoc_rowsum_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, v);
-  for (int step = 0; step <= kAssocSteps; ++step) {
-    hipLaunchKernelGGL(assoc_control_kernel, dim3(K), dim3(64), 0, st, step - 1, D, v);
-    launch_cholw(st, K, v);
-  }
-  hipLaunchKernelGGL(assoc_control_kernel, dim3(K), dim3(64), 0, st, kAssocSteps, D, v);
-  hipLaunchKernelGGL(covw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, v, A_out, min_eig_out);
   return launch_status();
 }
 
@@ -181,61 +106,6 @@ int uglad_conditional_mean(const float* precision, const float* mean, const floa
   return launch_status();
 }
 
-int uglad_conditional_mean_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, afterw_problem_floats); }
-
-int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,
-                                double* full_mean, float* cond_cov, double* log_pdf, float* workspace, int K, int D, int clip01,
-                                uglad_stream_t stream) {
-  if (!precision || !mean || !observed || !values || !full_mean || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
-  if (uglad_conditional_mean_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
-  hipStream_t st = (hipStream_t)stream;
-  const AfterwView v = afterw_view(workspace, D);
-  const AfterwIn in{precision, mean, observed, values};
-  const int nt = v.c.DP / kT64;
-  const dim3 rows(nt, K), tiles(nt, nt, K), wg(kWThreads);
-  hipLaunchKernelGGL(afterw_prepare_kernel, tiles, wg, 0, st, in, D, v);
-  hipLaunchKernelGGL(afterw_rhs_kernel, rows, dim3(64), 0, st, observed, D, v);
-  launch_cholw(st, K, v.c);
-  for (int i = 1; i < nt; ++i) hipLaunchKernelGGL(afterw_subst_kernel, dim3(i, K), wg, 0, st, i, v);
-  // y = W^T (W r); y += W^T (W (r - A y))
-  using V = AfterwView;
-  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwLower, (int)V::kR, (int)V::kT, 0, v);
-  hipLaunchKernelGGL(afterw_matvec_kernel<true>, rows, wg, 0, st, (int)kAfterwUpper, (int)V::kT, (int)V::kY, 0, v);
-  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwResidual, (int)V::kY, (int)V::kRes, 0, v);
-  hipLaunchKernelGGL(afterw_matvec_kernel<false>, rows, wg, 0, st, (int)kAfterwLower, (int)V::kRes, (int)V::kT, 0, v);
-  hipLaunchKernelGGL(afterw_matvec_kernel<true>, rows, wg, 0, st, (int)kAfterwUpper, (int)V::kT, (int)V::kY, 1, v);
-  if (cond_cov) hipLaunchKernelGGL(afterw_cov_kernel, tiles, wg, 0, st, observed, D, v, cond_cov);
-  hipLaunchKernelGGL(afterw_finish_kernel, rows, wg, 0, st, in, D, clip01, v, full_mean, log_pdf);
-  return launch_status();
-}
-
-int uglad_sample_scores_workspace_floats(int K, int N, int D) {
-  if (K < 1 || K > 65535 || N < 1 || D < 1 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
-  const size_t n = scorew_floats(K, N, D);
-  return n > 2147483647ULL ? UGLAD_E_DIM : (int)n;
-}
-
-int uglad_sample_scores(const double* X, int x_batch, const double* precision, const double* mean, double* mahalanobis,
-                        double* log_density, double* logdet, float* workspace, int K, int N, int D, uglad_stream_t stream) {
-  if (!X || !precision || !mean || !mahalanobis || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
-  if (uglad_sample_scores_workspace_floats(K, N, D) < 0 || (x_batch != 1 && x_batch != K)) return UGLAD_E_DIM;
-  hipStream_t st = (hipStream_t)stream;
-  const AfterwView v = afterw_view(workspace, D);
-  double* parts = scorew_partials(v, K);
-  const ScorewIn in{X, mean, x_batch, N, D};
-  const int nt = v.c.DP / kT64;
-  const dim3 wg(kWThreads);
-  hipLaunchKernelGGL(scorew_prepare_kernel, dim3(nt, nt, K), wg, 0, st, precision, D, v);
-  hipLaunchKernelGGL(scorew_quad_kernel, dim3((unsigned)((N + (size_t)kT64 - 1) / kT64), nt, K), wg, 0, st, in, v, parts);
-  if (log_density || logdet) {  // the factorisation only for those who read it
-    launch_cholw(st, K, v.c);
-    hipLaunchKernelGGL(scorew_logdet_kernel, dim3(K), wg, 0, st, D, v, logdet);
-  }
-  hipLaunchKernelGGL(scorew_finish_kernel, dim3((unsigned)((N + (size_t)kWThreads - 1) / kWThreads), K), wg, 0, st, N, D, v, parts, mahalanobis,
-                     log_density);
-  return launch_status();
-}
-
 int uglad_partial_correlations(const float* precision, float* rho, int K, int D, uglad_stream_t stream) {
   if (!precision || !rho) return UGLAD_E_NULL;
   if (K < 1 || D < 1) return UGLAD_E_DIM;
@@ -254,71 +124,6 @@ int uglad_support_metrics(const float* true_theta, const float* pred_theta, doub
     hipLaunchKernelGGL((support_metrics_kernel<decltype(nt)::value>), dim3(K), dim3(kThreads), 0, st, true_theta, pred_theta, out, D,
                                     beta);
   });
-  return launch_status();
-}
-
-int uglad_support_metrics_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 2, mw_pair_floats); }
-
-int uglad_support_metrics_wide(const float* true_theta, const float* pred_theta, double* out, float* workspace, int K, int D, int beta,
-                               uglad_stream_t stream) {
-  if (!true_theta || !pred_theta || !out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
-  if (uglad_support_metrics_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
-  hipStream_t st = (hipStream_t)stream;
-  const MwView v = mw_view(workspace, D);
-  const dim3 tiles(v.tiles, K), wg(kWThreads);
-  hipLaunchKernelGGL(mw_keys_kernel, dim3(v.nt, v.nt, K), wg, 0, st, true_theta, pred_theta, D, v);
-  for (int pass = 0; pass < kMwPasses; ++pass) {  // (an even number of passes: the sorted keys end in buffer 0)
-    hipLaunchKernelGGL(mw_hist_kernel, tiles, wg, 0, st, pass, pass & 1, v);
-    hipLaunchKernelGGL(mw_scan_kernel, dim3(K), wg, 0, st, v);
-    hipLaunchKernelGGL(mw_scatter_kernel, tiles, wg, 0, st, pass, pass & 1, v);
-  }
-  hipLaunchKernelGGL(mw_chunk_kernel, tiles, wg, 0, st, v);
-  hipLaunchKernelGGL(mw_group_kernel, tiles, wg, 0, st, v);
-  hipLaunchKernelGGL(mw_finish_kernel, dim3(K), wg, 0, st, out, beta, v);
-  return launch_status();
-}
-
-int uglad_graph_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 2, gw_problem_floats); }
-
-int uglad_graph_wide(const float* values, int from_precision, const int* n_keep, const float* threshold_in, float* threshold,
-                     int* edge_count, int* edge_ij, float* edge_w, int* degree, int* triangles2, double* stats, int want_stats, int K, int D,
-                     float* workspace, uglad_stream_t stream) {
-  if (!values || !n_keep || !threshold || !edge_count || !edge_ij || !edge_w || !degree || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
-  if (uglad_graph_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
-  if ((from_precision != 0 && from_precision != 1) || (want_stats != 0 && want_stats != 1)) return UGLAD_E_MODE;
-  if (want_stats && (!triangles2 || !stats)) return UGLAD_E_NULL;
-  const GwView v = gw_view(workspace, D);
-  bool ranked = false;
-  for (int k = 0; k < K; ++k) {
-    if (n_keep[k] < -1 || n_keep[k] > v.s.E) return UGLAD_E_DIM;
-    if (n_keep[k] == -1 && !threshold_in) return UGLAD_E_NULL;
-    ranked = ranked || n_keep[k] >= 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = v.s.nt;
-  const dim3 sort_tiles(v.s.tiles, K), tiles(nt, nt, K), wg(kWThreads);
-  if (ranked) {  // (a batch of given thresholds needs no order)
-    hipLaunchKernelGGL(gw_keys_kernel, tiles, wg, 0, st, values, from_precision, v);
-    for (int pass = 0; pass < kMwPasses; ++pass) {  // (an even number of passes: the sorted keys end in buffer 0)
-      hipLaunchKernelGGL(mw_hist_kernel, sort_tiles, wg, 0, st, pass, pass & 1, v.s);
-      hipLaunchKernelGGL(mw_scan_kernel, dim3(K), wg, 0, st, v.s);
-      hipLaunchKernelGGL(mw_scatter_kernel, sort_tiles, wg, 0, st, pass, pass & 1, v.s);
-    }
-  }
-  for (int k0 = 0; k0 < K; k0 += kGwKeepPer) {
-    GwKeep keep;
-    const int n = K - k0 < kGwKeepPer ? K - k0 : kGwKeepPer;
-    for (int q = 0; q < kGwKeepPer; ++q) keep.n[q] = q < n ? n_keep[k0 + q] : -1;
-    hipLaunchKernelGGL(gw_threshold_kernel, dim3(n), dim3(64), 0, st, keep, k0, threshold_in, threshold, v);
-  }
-  hipLaunchKernelGGL(gw_row_kernel, dim3(v.DP, K), wg, 0, st, values, from_precision, degree, v);
-  hipLaunchKernelGGL(gw_scan_kernel, dim3(K), wg, 0, st, edge_count, v);
-  hipLaunchKernelGGL(gw_edges_kernel, dim3(D, K), wg, 0, st, values, from_precision, edge_ij, edge_w, v);
-  if (want_stats) {
-    hipLaunchKernelGGL(gw_triangles_kernel, tiles, wg, 0, st, v);
-    hipLaunchKernelGGL(gw_rowsum_kernel, dim3((D + kWThreads - 1) / kWThreads, K), wg, 0, st, triangles2, v);
-    hipLaunchKernelGGL(gw_finish_kernel, dim3(K), wg, 0, st, degree, triangles2, stats, v);
-  }
   return launch_status();
 }
 

@@ -1,10 +1,11 @@
-// Host layer, part 1 of 5 (glad_kernels.hip, the manifest of the library, includes them in this order after the kernel headers and its
+// Host layer, part 1 of 6 (glad_kernels.hip, the manifest of the library, includes them in this order after the kernel headers and its
 // instantiation lists -- in the host unit and the single-unit build, not in the per-NT units; none of them holds device code):
 //   host_route.h   build limits, the run-time switches, the dispatch on NT, Route (which kernels a call launches), workspace layouts
 //   host_launch.h  the launch sequence of every path
 //   host_api.h     the extern "C" entry points of the pass: validate, build a Route, call host_launch.h
 //   host_rccl.h    RCCL as the exchange of the sharded pass
-//   host_extra.h   the utilities (symeig, covariance, conditional mean, ...) and the diagnostic exports
+//   host_extra.h   the one-workgroup utilities (symeig, covariance, conditional mean, ...) and the diagnostic exports
+//   host_wide.h    the many-workgroup fp64 utilities: their shared checks and launch chains, their entry points
 #pragma once
 #include <type_traits>
 using namespace uglad;

@@ -10,13 +10,9 @@
 //   mw_keys_kernel      one workgroup per 64 x 64 tile of the upper triangle (rows of the tile read along j): one 32-bit key per edge,
 //                       ((bits(pred) & 0x7fffffff) << 1) | label -- the sign bit of |x| is free, so unsigned key order is (score, label) order
 //                       and the positives close every tie group -- stored at the edge's row-major index; and the tile's counts T, P, TP
-//   8 x { mw_hist_kernel, mw_scan_kernel, mw_scatter_kernel }
-//                       least-significant-digit radix sort of the keys of each pair, 4 bits per pass, tiles of 2048 keys: the tile's 16 digit
-//                       counts; their exclusive scan in (digit, tile) order, one workgroup per pair; the stable scatter.  A thread holds 8
-//                       CONSECUTIVE keys and counts its digits in one 64-bit register (16 x 4 bits); the scan of the 16 x 256 counts in (digit,
-//                       thread) order is the key's place in the sorted tile, the tile is sorted in LDS and leaves in runs of equal digits.
-//                       No ballot, no atomics, no workgroup waits on another; every 32-bit value is a legal key (0xffffffff = |NaN|, label 1)
-//                       and the ragged last tile is handled by its count
+//   8 x { sortw_hist_kernel, sortw_scan_kernel, sortw_scatter_kernel }
+//                       the radix sort of sort_wide.h on the keys of each pair (launch_sortw); every 32-bit value is a legal key
+//                       (0xffffffff = |NaN|, label 1)
 //   mw_chunk_kernel     per 2048 sorted keys: the positives in the chunk, its last group boundary (where key >> 1 changes) and the positives
 //                       of the chunk in front of that boundary
 //   mw_group_kernel     per chunk: what lies in front of it from the chunk records (positives; the start a of the tie group that reaches into
@@ -32,104 +28,33 @@
 // them) sort by their bit pattern above every finite score; the call terminates and returns what that order gives.
 // 4 + 3 x 8 launches in one linear chain, no host readback.
 #pragma once
-#include "wide_bwd.h"
+#include "sort_wide.h"
 
 namespace uglad {
 
-constexpr int kMwBits = 4, kMwBins = 1 << kMwBits, kMwPasses = 32 / kMwBits;
-constexpr int kMwPer = 8;                      // consecutive keys per thread: a digit's count in a thread fits 4 bits
-constexpr int kMwTile = kWThreads * kMwPer;    // keys per workgroup
-constexpr int kMwKeyTile = 64;                 // tile of the upper triangle in mw_keys_kernel
-static_assert(kWThreads == 256 && kMwBins * kMwBits == 64 && kMwPer < kMwBins, "a thread's digit counts share one 64-bit register");
+constexpr int kMwKeyTile = 64;  // tile of the upper triangle in mw_keys_kernel
 
 // One pair's part of the workspace in 4-byte words (the buffer is 8-byte aligned and every part even, so the 64-bit parts stay aligned):
-//   keys 0 | keys 1   E words each, rounded up to even: the sort's two buffers (the sorted keys end in buffer 0)
-//   hist   16 x tiles   digit counts of the pass, then their exclusive scan, (digit, tile) order
+//   keys 0 | keys 1 | hist   the sort's part (SortwView, sort_wide.h)
 //   kpart  nt x nt x 4  T, P, TP of every tile of mw_keys_kernel
 //   chunk  tiles x 4    positives, last boundary (-1: none), positives in front of it
 //   mw2    tiles int64 | ap   tiles fp64
 struct MwView {
-  unsigned* ws;
-  size_t pair;  // words per pair
-  int E, tiles, nt;
-  __host__ __device__ size_t epad() const { return ((size_t)E + 1) & ~(size_t)1; }
-  __host__ __device__ unsigned* keys(int k, int which) const { return ws + (size_t)k * pair + (size_t)which * epad(); }
-  __host__ __device__ int* hist(int k) const { return reinterpret_cast<int*>(keys(k, 2)); }
-  __host__ __device__ int* kpart(int k) const { return hist(k) + (size_t)kMwBins * tiles; }
+  SortwView s;
+  int nt;
+  __host__ __device__ int* kpart(int k) const { return s.behind(k); }
   __host__ __device__ int* chunk(int k) const { return kpart(k) + 4 * (size_t)nt * nt; }
-  __host__ __device__ long long* mw2(int k) const { return reinterpret_cast<long long*>(chunk(k) + 4 * (size_t)tiles); }
-  __host__ __device__ double* ap(int k) const { return reinterpret_cast<double*>(mw2(k) + tiles); }
+  __host__ __device__ long long* mw2(int k) const { return reinterpret_cast<long long*>(chunk(k) + 4 * (size_t)s.tiles); }
+  __host__ __device__ double* ap(int k) const { return reinterpret_cast<double*>(mw2(k) + s.tiles); }
 };
 __host__ __device__ constexpr size_t mw_pair_words(size_t E, size_t tiles, size_t nt) {
-  return 2 * ((E + 1) & ~(size_t)1) + kMwBins * tiles + 4 * nt * nt + 4 * tiles + 2 * tiles + 2 * tiles;
+  return sortw_words(E, tiles) + 4 * nt * nt + 4 * tiles + 2 * tiles + 2 * tiles;
 }
 __host__ inline MwView mw_view(float* workspace, int D) {
-  const int E = D * (D - 1) / 2, tiles = (E + kMwTile - 1) / kMwTile, nt = (D + kMwKeyTile - 1) / kMwKeyTile;
-  return MwView{reinterpret_cast<unsigned*>(workspace), mw_pair_words((size_t)E, (size_t)tiles, (size_t)nt), E, tiles, nt};
+  const int E = D * (D - 1) / 2, tiles = sortw_tiles(E), nt = (D + kMwKeyTile - 1) / kMwKeyTile;
+  return MwView{SortwView{reinterpret_cast<unsigned*>(workspace), mw_pair_words((size_t)E, (size_t)tiles, (size_t)nt), E, tiles}, nt};
 }
-__host__ inline size_t mw_pair_floats(int D) { return mw_view(nullptr, D).pair; }
-
-// ---------------------------------------------------------------------------------------------------------------- workgroup helpers
-// (256 threads = 4 waves; s_w: 4 ints of LDS; the first barrier protects s_w's previous use)
-__device__ __forceinline__ int mw_block_sum(int v, int* s_w) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-__device__ __forceinline__ int mw_block_max(int v, int* s_w) {
-  for (int m = 32; m >= 1; m >>= 1) {
-    const int o = __shfl_xor(v, m);
-    v = o > v ? o : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int a = s_w[0] > s_w[1] ? s_w[0] : s_w[1], b = s_w[2] > s_w[3] ? s_w[2] : s_w[3];
-  return a > b ? a : b;
-}
-// exclusive prefix in thread order: kMax = false the sum (identity 0), kMax = true the maximum (identity -1)
-template <bool kMax>
-__device__ __forceinline__ int mw_block_scan(int v, int* s_w) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  auto op = [](int a, int b) { return kMax ? (a > b ? a : b) : a + b; };
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl(inc, lane - d);
-    if (lane >= d) inc = op(inc, o);
-  }
-  int prev = __shfl(inc, lane - 1);  // the wave's exclusive prefix
-  if (lane == 0) prev = kMax ? -1 : 0;
-  __syncthreads();
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  int before = kMax ? -1 : 0;
-  for (int q = 0; q < 3; ++q)
-    if (q < w) before = op(before, s_w[q]);
-  return op(before, prev);
-}
-
-// the thread's kMwPer consecutive keys of tile `tile`; returns how many of them exist (the ragged tail: by count, no sentinel)
-__device__ __forceinline__ int mw_load(const unsigned* __restrict__ keys, int E, int tile, unsigned (&key)[kMwPer]) {
-  const int g0 = tile * kMwTile + (int)threadIdx.x * kMwPer;
-  if (g0 + kMwPer <= E) {  // (g0 is even and so is every buffer's offset: 8-byte aligned)
-    __builtin_memcpy(key, __builtin_assume_aligned(keys + g0, 8), sizeof(unsigned) * kMwPer);
-    return kMwPer;
-  }
-#pragma unroll
-  for (int j = 0; j < kMwPer; ++j) key[j] = g0 + j < E ? keys[g0 + j] : 0u;
-  return E - g0 > 0 ? E - g0 : 0;
-}
-__device__ __forceinline__ int mw_digit(unsigned key, int pass) { return (int)((key >> (kMwBits * pass)) & (kMwBins - 1)); }
-// the thread's 16 digit counts, 4 bits each
-__device__ __forceinline__ unsigned long long mw_count(const unsigned (&key)[kMwPer], int n, int pass) {
-  unsigned long long packed = 0;
-#pragma unroll
-  for (int j = 0; j < kMwPer; ++j)
-    if (j < n) packed += 1ull << (kMwBits * mw_digit(key[j], pass));
-  return packed;
-}
+__host__ inline size_t mw_pair_floats(int D) { return mw_view(nullptr, D).s.stride; }
 
 // ---------------------------------------------------------------------------------------------------------------- keys and counts
 // grid (nt, nt, K): tile (I, J) = (blockIdx.y, blockIdx.x) of 64 x 64; tiles below the diagonal only zero their counts
@@ -143,7 +68,7 @@ __global__ __launch_bounds__(kWThreads) void mw_keys_kernel(const float* __restr
     return;
   }
   const size_t base = (size_t)k * D * D;
-  unsigned* keys = v.keys(k, 0);
+  unsigned* keys = v.s.keys(k, 0);
   const int j = J * kMwKeyTile + (tid & 63);
   int n_true = 0, n_pred = 0, n_both = 0;
   for (int r = tid >> 6; r < kMwKeyTile; r += 4) {
@@ -158,104 +83,23 @@ __global__ __launch_bounds__(kWThreads) void mw_keys_kernel(const float* __restr
       n_both += label && mag != 0u;
     }
   }
-  n_true = mw_block_sum(n_true, s_w);
-  n_pred = mw_block_sum(n_pred, s_w);
-  n_both = mw_block_sum(n_both, s_w);
+  n_true = sortw_block_sum(n_true, s_w);
+  n_pred = sortw_block_sum(n_pred, s_w);
+  n_both = sortw_block_sum(n_both, s_w);
   if (tid == 0) part[0] = n_true, part[1] = n_pred, part[2] = n_both, part[3] = 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- one pass of the sort
-// grid (tiles, K): hist[digit][tile] = keys of the tile with that digit
-__global__ __launch_bounds__(kWThreads) void mw_hist_kernel(int pass, int src, MwView v) {
-  constexpr int kRow = kWThreads + 16;  // (row stride 16 mod 64: the four digits a wave sums at once sit in different banks)
-  __shared__ int s_cnt[kMwBins * kRow];
-  const int tile = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
-  unsigned key[kMwPer];
-  const int n = mw_load(v.keys(k, src), v.E, tile, key);
-  const unsigned long long packed = mw_count(key, n, pass);
-#pragma unroll
-  for (int d = 0; d < kMwBins; ++d) s_cnt[d * kRow + tid] = (int)((packed >> (kMwBits * d)) & 15);
-  __syncthreads();
-  // 16 threads per digit, each 16 of the 256 counts; the 16 partial sums meet by a butterfly inside the 16 lanes
-  const int d = tid >> 4, seg = tid & 15;
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s += s_cnt[d * kRow + i * 16 + seg];
-  for (int m = 8; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  if (seg == 0) v.hist(k)[(size_t)d * v.tiles + tile] = s;
-}
-
-// grid (K): the exclusive scan of hist in (digit, tile) order, in place: where the tile's keys with that digit go
-__global__ __launch_bounds__(kWThreads) void mw_scan_kernel(MwView v) {
-  __shared__ int s_w[4];
-  int* h = v.hist(blockIdx.x);
-  const int n = kMwBins * v.tiles, per = (n + kWThreads - 1) / kWThreads;
-  const int lo = (int)threadIdx.x * per < n ? (int)threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += h[i];
-  int run = mw_block_scan<false>(s, s_w);
-  for (int i = lo; i < hi; ++i) {
-    const int c = h[i];
-    h[i] = run;
-    run += c;
-  }
-}
-
-// grid (tiles, K): stable scatter of the tile by the pass's digit
-__global__ __launch_bounds__(kWThreads) void mw_scatter_kernel(int pass, int src, MwView v) {
-  __shared__ int s_cnt[kMwBins * kWThreads + kWThreads];  // entry i = (digit, thread) at i + (i >> 4): 16 consecutive entries per thread, no bank conflicts
-  __shared__ unsigned s_key[kMwTile];
-  __shared__ int s_w[4], s_start[kMwBins], s_dst[kMwBins];
-  const int tile = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
-  auto at = [](int i) { return i + (i >> 4); };
-  unsigned key[kMwPer];
-  const int n = mw_load(v.keys(k, src), v.E, tile, key);
-  const unsigned long long packed = mw_count(key, n, pass);
-#pragma unroll
-  for (int d = 0; d < kMwBins; ++d) s_cnt[at(d * kWThreads + tid)] = (int)((packed >> (kMwBits * d)) & 15);
-  if (tid < kMwBins) s_dst[tid] = v.hist(k)[(size_t)tid * v.tiles + tile];
-  __syncthreads();
-  // exclusive scan of the 4096 counts in (digit, thread) order = place in the sorted tile of the thread's first key with that digit
-  int c[16], s = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s += c[i] = s_cnt[at(16 * tid + i)];
-  int run = mw_block_scan<false>(s, s_w);
-  if ((tid & 15) == 0) s_start[tid >> 4] = run;  // where the digit's run starts in the sorted tile
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    s_cnt[at(16 * tid + i)] = run;
-    run += c[i];
-  }
-  __syncthreads();
-  unsigned long long seen = 0;
-#pragma unroll
-  for (int j = 0; j < kMwPer; ++j)
-    if (j < n) {
-      const int d = mw_digit(key[j], pass);
-      s_key[s_cnt[at(d * kWThreads + tid)] + (int)((seen >> (kMwBits * d)) & 15)] = key[j];
-      seen += 1ull << (kMwBits * d);
-    }
-  __syncthreads();
-  const int left = v.E - tile * kMwTile, valid = left < kMwTile ? left : kMwTile;
-  unsigned* dst = v.keys(k, src ^ 1);
-  for (int q = tid; q < valid; q += kWThreads) {
-    const unsigned x = s_key[q];
-    const int d = mw_digit(x, pass);
-    dst[s_dst[d] + (q - s_start[d])] = x;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- group statistics
-// what a thread sees in its kMwPer sorted keys: positives, the last group boundary (index in the thread, -1: none) and the positives in front of it
+// what a thread sees in its kSortwPer sorted keys: positives, the last group boundary (index in the thread, -1: none) and the positives in front of it
 struct MwRun {
   int npos, last, pos_before_last;
   unsigned bounds;  // bit j: key j starts a tie group
 };
-__device__ __forceinline__ MwRun mw_run(const unsigned* __restrict__ keys, const unsigned (&key)[kMwPer], int n, int g0) {
+__device__ __forceinline__ MwRun mw_run(const unsigned* __restrict__ keys, const unsigned (&key)[kSortwPer], int n, int g0) {
   MwRun r{0, -1, 0, 0u};
   unsigned prev = (n > 0 && g0 > 0) ? keys[g0 - 1] : 0u;
 #pragma unroll
-  for (int j = 0; j < kMwPer; ++j)
+  for (int j = 0; j < kSortwPer; ++j)
     if (j < n) {
       if (g0 + j == 0 || (key[j] >> 1) != (prev >> 1)) r.bounds |= 1u << j, r.last = j, r.pos_before_last = r.npos;
       r.npos += (int)(key[j] & 1u);
@@ -268,16 +112,16 @@ __device__ __forceinline__ MwRun mw_run(const unsigned* __restrict__ keys, const
 __global__ __launch_bounds__(kWThreads) void mw_chunk_kernel(MwView v) {
   __shared__ int s_w[4];
   const int c = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
-  const unsigned* keys = v.keys(k, 0);
-  unsigned key[kMwPer];
-  const int n = mw_load(keys, v.E, c, key);
-  const MwRun r = mw_run(keys, key, n, c * kMwTile + tid * kMwPer);
-  const int before = mw_block_scan<false>(r.npos, s_w);
-  const int owner = mw_block_max(r.last >= 0 ? tid : -1, s_w);  // the last thread that holds a boundary
+  const unsigned* keys = v.s.keys(k, 0);
+  unsigned key[kSortwPer];
+  const int n = sortw_load(keys, v.s.E, c, key);
+  const MwRun r = mw_run(keys, key, n, c * kSortwTile + tid * kSortwPer);
+  const int before = sortw_block_scan<false>(r.npos, s_w);
+  const int owner = sortw_block_max(r.last >= 0 ? tid : -1, s_w);  // the last thread that holds a boundary
   int* rec = v.chunk(k) + 4 * c;
   if (tid == kWThreads - 1) rec[0] = before + r.npos, rec[3] = 0;
   if (owner < 0 && tid == 0) rec[1] = -1, rec[2] = 0;
-  if (tid == owner) rec[1] = tid * kMwPer + r.last, rec[2] = before + r.pos_before_last;
+  if (tid == owner) rec[1] = tid * kSortwPer + r.last, rec[2] = before + r.pos_before_last;
 }
 
 // grid (tiles, K): the chunk's share of MW2 and of the sum of AP
@@ -289,7 +133,7 @@ __global__ __launch_bounds__(kWThreads) void mw_group_kernel(MwView v) {
   const int* rec = v.chunk(k);
   // in front of the chunk: the positives, and the last chunk with a boundary (chunk 0 starts a group: there is one for every c > 0)
   int pos_in = 0, all = 0, cb = -1;
-  for (int q = tid; q < v.tiles; q += kWThreads) {
+  for (int q = tid; q < v.s.tiles; q += kWThreads) {
     const int np = rec[4 * q];
     all += np;
     if (q < c) {
@@ -297,35 +141,35 @@ __global__ __launch_bounds__(kWThreads) void mw_group_kernel(MwView v) {
       if (rec[4 * q + 1] >= 0) cb = q;
     }
   }
-  pos_in = mw_block_sum(pos_in, s_w);
-  const int T = mw_block_sum(all, s_w);
-  cb = mw_block_max(cb, s_w);
+  pos_in = sortw_block_sum(pos_in, s_w);
+  const int T = sortw_block_sum(all, s_w);
+  cb = sortw_block_max(cb, s_w);
   int a_in = 0, pa_in = 0;  // start of the group that reaches into the chunk and the positives in front of that start
   if (cb >= 0) {            // (uniform per workgroup)
     int s = 0;
     for (int q = tid; q < cb; q += kWThreads) s += rec[4 * q];
-    a_in = cb * kMwTile + rec[4 * cb + 1];
-    pa_in = mw_block_sum(s, s_w) + rec[4 * cb + 2];
+    a_in = cb * kSortwTile + rec[4 * cb + 1];
+    pa_in = sortw_block_sum(s, s_w) + rec[4 * cb + 2];
   }
-  const unsigned* keys = v.keys(k, 0);
-  unsigned key[kMwPer];
-  const int n = mw_load(keys, v.E, c, key);
-  const int g0 = c * kMwTile + tid * kMwPer;
+  const unsigned* keys = v.s.keys(k, 0);
+  unsigned key[kSortwPer];
+  const int n = sortw_load(keys, v.s.E, c, key);
+  const int g0 = c * kSortwTile + tid * kSortwPer;
   const MwRun r = mw_run(keys, key, n, g0);
-  int pos = pos_in + mw_block_scan<false>(r.npos, s_w);  // positives in front of the thread's first key
+  int pos = pos_in + sortw_block_scan<false>(r.npos, s_w);  // positives in front of the thread's first key
   s_a[tid] = g0 + r.last;
   s_pa[tid] = pos + r.pos_before_last;
-  const int owner = mw_block_scan<true>(r.last >= 0 ? tid : -1, s_w);  // (its barriers publish s_a / s_pa) the last earlier thread with a boundary
+  const int owner = sortw_block_scan<true>(r.last >= 0 ? tid : -1, s_w);  // (its barriers publish s_a / s_pa) the last earlier thread with a boundary
   int a = owner >= 0 ? s_a[owner] : a_in, pa = owner >= 0 ? s_pa[owner] : pa_in;
   long long mw = 0;
   double ap = 0.0;
 #pragma unroll
-  for (int j = 0; j < kMwPer; ++j)
+  for (int j = 0; j < kSortwPer; ++j)
     if (j < n) {
       if ((r.bounds >> j) & 1u) a = g0 + j, pa = pos;
       if (key[j] & 1u) {
         mw += (long long)(a - pa) + (long long)(g0 + j - pos);
-        ap += (double)(T - pa) / (double)(v.E - a);
+        ap += (double)(T - pa) / (double)(v.s.E - a);
         ++pos;
       }
     }
@@ -351,19 +195,19 @@ __global__ __launch_bounds__(kWThreads) void mw_finish_kernel(double* __restrict
   const int* part = v.kpart(k);
   int n_true = 0, n_pred = 0, n_both = 0;
   for (int q = tid; q < v.nt * v.nt; q += kWThreads) n_true += part[4 * q], n_pred += part[4 * q + 1], n_both += part[4 * q + 2];
-  const long long Tn = mw_block_sum(n_true, s_w), Pn = mw_block_sum(n_pred, s_w), TP = mw_block_sum(n_both, s_w);
+  const long long Tn = sortw_block_sum(n_true, s_w), Pn = sortw_block_sum(n_pred, s_w), TP = sortw_block_sum(n_both, s_w);
   // the chunks' partial sums in index order: 256 at a time through LDS (one thread adds, all threads fetch)
   long long MW2 = 0;
   double AP = 0.0;
-  for (int c0 = 0; c0 < v.tiles; c0 += kWThreads) {
+  for (int c0 = 0; c0 < v.s.tiles; c0 += kWThreads) {
     __syncthreads();
-    if (c0 + tid < v.tiles) s_mw[tid] = v.mw2(k)[c0 + tid], s_ap[tid] = v.ap(k)[c0 + tid];
+    if (c0 + tid < v.s.tiles) s_mw[tid] = v.mw2(k)[c0 + tid], s_ap[tid] = v.ap(k)[c0 + tid];
     __syncthreads();
     if (tid == 0)
-      for (int q = 0; q < kWThreads && c0 + q < v.tiles; ++q) MW2 += s_mw[q], AP += s_ap[q];
+      for (int q = 0; q < kWThreads && c0 + q < v.s.tiles; ++q) MW2 += s_mw[q], AP += s_ap[q];
   }
   if (tid == 0) {
-    const double dTP = (double)TP, dP = (double)Pn, dT = (double)Tn, dF = (double)v.E - dT;
+    const double dTP = (double)TP, dP = (double)Pn, dT = (double)Tn, dF = (double)v.s.E - dT;
     const double FP = dP - dTP, FN = dT - dTP;
     const double b2 = (double)beta * (double)beta;
     double* o = out + (size_t)k * 11;

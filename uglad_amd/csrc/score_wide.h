@@ -19,8 +19,7 @@
 //   cholw_update_kernel, cholw_panel_kernel<CholwInvView>
 //                           (only when the caller wants log_density or logdet) P = L L^T on after_wide.h's layout, whose view carries the
 //                           log-pivots (chol_wide.h).  A pivot that is <= 0 or NaN raises the model's flag
-//   scorew_logdet_kernel    logdet P = the D log-pivots, 256 strided partial sums combined in thread order (as afterw_finish_kernel); NaN
-//                           for a flagged model
+//   scorew_logdet_kernel    logdet P = the D log-pivots (cholw_log_pivot_sum, as afterw_finish_kernel); NaN for a flagged model
 //   scorew_finish_kernel    q[n] = the partials summed over J = 0 .. DP / 64 - 1 in ascending order, then the log-density
 //
 // THE BITWISE PROPERTY.  A row's two numbers depend on that row and the model alone: not on N, not on the row's position in the table, not
@@ -38,9 +37,9 @@ namespace uglad {
 // The workspace, in DOUBLES (the buffer is 8-byte aligned): K problems of after_wide.h's layout (A = P, L, the control block, the log-pivots;
 // vector 0 of vec3 carries logdet P in its first element), and behind them the partials, (K, DP / 64, NP) with NP = N rounded up to 64.
 __host__ __device__ constexpr size_t scorew_padded_rows(int N) { return ((size_t)N + kT64 - 1) / kT64 * kT64; }
-__host__ inline size_t scorew_floats(int K, int N, int D) {
+__host__ inline size_t scorew_model_floats(int N, int D) {  // (per model: its problem and its partials; the K problems lie in front of all partials)
   const int DP = t64_padded(D);
-  return 2 * ((size_t)K * afterw_problem_doubles(DP) + (size_t)K * (DP / kT64) * scorew_padded_rows(N));
+  return 2 * (afterw_problem_doubles(DP) + (size_t)(DP / kT64) * scorew_padded_rows(N));
 }
 __host__ inline double* scorew_partials(const AfterwView& v, int K) { return v.c.base + (size_t)K * v.c.stride; }
 
@@ -114,16 +113,8 @@ __global__ __launch_bounds__(kWThreads) void scorew_logdet_kernel(int D, AfterwV
   __shared__ double s_sum[kWThreads];
   const int t = blockIdx.x, tid = threadIdx.x;
   const bool ok = cholw_gate(v.c.ctl(t));
-  const double* lp = v.c.log_pivot(t);
-  double s = 0.0;
-  if (ok)
-    for (int k = tid; k < D; k += kWThreads) s += lp[k];
-  s_sum[tid] = s;
-  __syncthreads();
+  const double sum = cholw_log_pivot_sum(v.c, t, D, ok, s_sum);
   if (tid == 0) {
-    double sum = 0.0;
-    for (int k = 0; k < kWThreads; ++k) sum += s_sum[k];
-    if (!ok) sum = __builtin_nan("");
     v.vec(t, AfterwView::kR)[0] = sum;
     if (logdet_out) logdet_out[t] = sum;
   }
