@@ -10,7 +10,10 @@ A CASE is (entry point, M, D, input):
           "neg3"   three: NaN loss (torch.logdet of a negative determinant), finite inverse
           "pivot0" A[0, 0] = 0: the first pivot is zero, NaN everywhere (the not-ok path)
 A FORM is the value of UGLAD_LDL_LAUNCHES: "0" one workgroup per matrix (ns_ldl_kernel), "1" one launch per phase (ns_ldl_phase_kernel), None unset
-(host_route.h decides: launches from nt = ceil(D / 32) = 9)."""
+(host_route.h decides: launches from nt = ceil(D / 32) = 9).
+
+The second half of the file is what test_ldl_hard.py and scripts/ldl_probe.py --hard share: hard_matrix (ill-conditioned, indefinite, scaled, graded
+and shifted inputs from a seed), run_on (one call on any input) and reference64 (the fp64 reference and the two error bounds, from the input alone)."""
 import os
 import zlib
 
@@ -102,12 +105,17 @@ def factored(case):
 
 def run(lib, dev, case, form):
     """(X (M, D, D), loss (M,) or None) of one call under one form, as numpy float32."""
-    entry, M, D, _ = case
+    return run_on(lib, dev, case[0], matrices(case), form, s_identity=True)
+
+
+def run_on(lib, dev, entry, A, form, s_identity=False):
+    """The same for any (M, D, D) float32 input.  "loss" with S = 0 unless s_identity, so that the loss IS -logdet (its trace term is an exact 0)."""
+    M, D, _ = A.shape
     saved = os.environ.pop(SWITCH, None)  # (the host layer reads its switches on every call)
     if form is not None:
         os.environ[SWITCH] = form
     try:
-        A = torch.from_numpy(matrices(case).copy()).to(dev)
+        A = torch.from_numpy(np.array(A, dtype=np.float32)).to(dev)
         X = torch.zeros_like(A)
         wsp = lib.workspace(M, D, A)
         loss = None
@@ -115,7 +123,8 @@ def run(lib, dev, case, form):
             lib.init_theta(A, packed_params()[0].to(dev), 0, X, wsp)
         else:
             loss = torch.zeros(M, dtype=torch.float32, device=dev)
-            lib.loss_fwd(A, torch.eye(D, dtype=torch.float32, device=dev)[None].contiguous(), None, loss, X, wsp)
+            S = torch.eye(D, dtype=torch.float32, device=dev) if s_identity else torch.zeros(D, D, dtype=torch.float32, device=dev)
+            lib.loss_fwd(A, S[None].contiguous(), None, loss, X, wsp)
         if dev != "cpu":
             torch.cuda.synchronize()
         return X.cpu().numpy().copy(), None if loss is None else loss.cpu().numpy().copy()
@@ -178,3 +187,179 @@ def within_twice(got, parent):
     got, parent = np.asarray(got, dtype=np.float64), np.asarray(parent, dtype=np.float64)
     nan = np.isnan(parent)
     return np.array_equal(np.isnan(got), nan) and bool(np.all(got[~nan] <= 2 * parent[~nan]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Hard matrices (test_ldl_hard.py, scripts/ldl_probe.py --hard): inputs from a seed, references and bounds in numpy fp64 from the input alone.
+U32 = 2.0 ** -24  # unit roundoff of fp32
+# "loss" kinds -> lib.loss_fwd with S = 0; Q diag(w) Q^T with a random orthogonal Q unless said otherwise
+SPD_KINDS = ("spd_1e2", "spd_1e3", "spd_1e4", "spd_1e5")               # w = logspace(0, -k)
+FLIP_KINDS = ("flip2_1e2", "flip40_1e2", "flip80_1e3", "flip40_1e4")   # ... with that many random signs flipped
+SCALED_KINDS = ("scaled_down", "scaled_up")                           # w = linspace(.5, 5) * 1e-3 | * 1e3
+A00_KINDS = ("a00_1e-2", "a00_1e-4", "a00_1e-6")                       # w = linspace(.5, 5), w[:3] = (-1, -3, .5), then A[0, 0] := that: a tiny first pivot
+SHIFTED_KINDS = ("shifted", "shifted_pos")                             # "init" kinds -> lib.init_theta with the trained t < 0 (see hard_matrix)
+FAMILIES = SPD_KINDS + FLIP_KINDS + SCALED_KINDS + A00_KINDS + ("graded",) + SHIFTED_KINDS  # every finite kind of the error table
+NOT_FINITE_KINDS = ("neg3", "pivot0")                                  # NaN loss, finite inverse | NaN throughout
+# where bound 2 must itself be small to say anything (test_ldl_hard.py asserts it is below LOGDET_CAP there); the rest have element growth
+LOGDET_CAPPED = SPD_KINDS + SCALED_KINDS + ("graded", "flip2_1e2", "a00_1e-2", "a00_1e-4", "shifted_pos")
+LOGDET_CAP = 0.1
+SPD_SHORTCUT_BEYOND = 577  # beyond this D the bounds of an spd input take sqrt(a_ii a_jj) for (|L| |d| |L|^T)_ij: no Python factorisation
+
+
+def logdet_capped(kind, D):
+    """Whether bound 2 must be below LOGDET_CAP for this input.  The bound grows like D cond(A): at cond 1e5 it is 6.8e-2 at D = 129, 9.2e-2 at
+    161 and 5.6e-1 at 577 whatever the device does, so that one kind is capped up to 161 only (beyond, the inequality alone is asserted)."""
+    return kind in LOGDET_CAPPED and (kind != "spd_1e5" or D <= 161)
+SIGN_AT = (5, 40, 70, 100, 128)  # test 7: rows of the negative pivots, one per 32-block 0 .. 4
+BATCH_KINDS = (("spd_1e2", 0), ("pivot0", 0), ("flip40_1e2", 0), ("neg3", 0), ("spd_1e2", 1))  # test 6: (kind, seed offset) of the M = 5 call
+
+
+def entry_of(kind):
+    return "init" if kind in SHIFTED_KINDS else "loss"
+
+
+def _orthogonal(D, seed):
+    key = ("Q", D, seed)
+    if key not in _cache:
+        _cache[key] = np.linalg.qr(np.random.default_rng(seed).standard_normal((D, D)))[0]
+    return _cache[key]
+
+
+def hard_matrix(kind, D, seed):
+    """(D, D) float32, read-only, computed once: the input of kind `kind` (the tuples above; "sign<k>": test 7's matrix with k negative pivots)."""
+    key = ("hard", kind, D, seed)
+    if key in _cache:
+        return _cache[key]
+    rng = np.random.default_rng([seed, D, zlib.crc32(kind.encode())])
+    lin = np.linspace(0.5, 5.0, D)
+    if kind.startswith("sign"):
+        # exactly T diag(w) T^T with T unit lower triangular and well conditioned: the unpivoted pivots ARE w, the negative ones at SIGN_AT
+        w = rng.permutation(lin)
+        w[list(SIGN_AT[:int(kind[4:])])] *= -1.0
+        T = np.eye(D) + np.tril(rng.standard_normal((D, D)), -1) * (0.3 / np.sqrt(D))
+        a = (T * w) @ T.T
+    else:
+        Q = _orthogonal(D, seed)
+        if kind in SPD_KINDS + FLIP_KINDS:
+            flips, cond = kind.split("_")
+            w = np.logspace(0.0, -float(cond[2:]), D)
+            if flips != "spd":
+                w[rng.choice(D, int(flips[4:]), replace=False)] *= -1.0
+        elif kind in SCALED_KINDS:
+            w = lin * (1e-3 if kind == "scaled_down" else 1e3)
+        elif kind in A00_KINDS or kind in NOT_FINITE_KINDS:
+            w = lin.copy()
+            w[:3] = (-1.0, -3.0, -0.7) if kind == "neg3" else (-1.0, -3.0, 0.5) if kind in A00_KINDS else w[:3]
+        elif kind == "graded":
+            w = lin
+        elif kind in SHIFTED_KINDS:
+            # a covariance whose smallest eigenvalues (1e-4: a repair offset) lie below |t| = 7.35e-4: S + t I is indefinite with ten tiny negative
+            # eigenvalues; "_pos": every eigenvalue of S >= 1e-2, S + t I positive
+            w = np.logspace(0.0, -3.0 if kind == "shifted" else -2.0, D)
+            if kind == "shifted":
+                w[-10:] = 1e-4
+        else:
+            raise ValueError(kind)
+        a = (Q * w) @ Q.T
+        if kind in A00_KINDS:
+            # lowering A[0, 0] is a negative rank-one change: it adds a third negative eigenvalue, det < 0 and no log-determinant to compare,
+            # wherever (A^-1)_00 > 1 / (A_00 - that).  Then w[1] = +3: one negative eigenvalue before, two after
+            a[0, 0] = float(kind[4:])
+            if np.linalg.slogdet(a)[0] < 0:
+                w[1] = 3.0
+                a = (Q * w) @ Q.T
+                a[0, 0] = float(kind[4:])
+        elif kind == "pivot0":
+            a[0, 0] = 0.0
+        elif kind == "graded":
+            s = rng.permutation(np.logspace(-1.5, 1.5, D))
+            a = a * np.outer(s, s)
+    a = np.ascontiguousarray((a + a.T) / 2, dtype=np.float32)
+    a.setflags(write=False)
+    _cache[key] = a
+    return a
+
+
+def inverted(kind, a32):
+    """(D, D) float64: the matrix the device inverts, from the fp32 input (plus the fp32 t on the diagonal for an "init" kind, as factored())."""
+    A = np.asarray(a32, dtype=np.float64)
+    return A + packed_params()[1] * np.eye(len(A)) if entry_of(kind) == "init" else A
+
+
+def shifted32(a32):
+    """(D, D) float32: a32 + t on the diagonal in fp32, what kLdlInit forms -- through "loss" it gives the log-determinant "init" does not return."""
+    a = np.array(a32, dtype=np.float32)
+    a[np.diag_indices(len(a))] += np.float32(packed_params()[1])
+    return a
+
+
+def ldl64(A, nb=64):
+    """(L, d) of the unpivoted A = L diag(d) L^T in fp64: rank-1 updates inside a panel of nb columns, one product per panel behind it."""
+    A = np.array(A, dtype=np.float64)
+    n = len(A)
+    L, d = np.eye(n), np.empty(n)
+    with np.errstate(all="ignore"):
+        for j in range(0, n, nb):
+            e = min(j + nb, n)
+            for k in range(j, e):
+                d[k] = A[k, k]
+                L[k + 1:, k] = A[k + 1:, k] / d[k]
+                A[k + 1:, k + 1:e] -= np.outer(L[k + 1:, k], A[k, k + 1:e])
+            A[e:, e:] -= (L[e:, j:e] * d[j:e]) @ L[e:, j:e].T
+    return L, d
+
+
+def pivots64(A, spd=False):
+    """d alone; spd: from Cholesky, no Python loop."""
+    return np.diag(np.linalg.cholesky(A)) ** 2 if spd else ldl64(A)[1]
+
+
+def sum_term(d):
+    """u sqrt(D) max_k |sum_{i<=k} ln |d_i||: what the fp32 running sum of the log-pivots can lose."""
+    return float(U32 * np.sqrt(len(d)) * np.abs(np.cumsum(np.log(np.abs(d)))).max())
+
+
+def reference64(A, spd=False):
+    """Everything the bounds need, in fp64 from A alone: X = A^-1, d = the unpivoted pivots, G >= |L| |d| |L|^T (spd: sqrt(a_ii a_jj), which bounds
+    it, and d from Cholesky: no Python loop), growth = max G / max |A|, logdet = log|det A| or NaN for det < 0, and the two bounds at c = 1:
+      inv_unit  u || |X| |A| |X| ||_F / ||X||_F       first-order error of one fp32 evaluation of X + X (I - A X) at the fixed point
+      sum_term  u sqrt(D) max_k |sum_{i<=k} ln |d_i||  the fp32 running sum of the log-pivots
+      ld_bound  u sum_ij |X|_ij G_ij + sum_term + ulp32(logdet) / 2: tr(A^-1 dA) under an unpivoted factorisation's backward error |dA| <= u G."""
+    D = len(A)
+    X = np.linalg.inv(A)
+    if spd:
+        d = pivots64(A, spd=True)
+        G = np.sqrt(np.outer(np.diag(A), np.diag(A)))
+    else:
+        L, d = ldl64(A)
+        G = (np.abs(L) * np.abs(d)) @ np.abs(L).T
+    aX = np.abs(X)
+    sign, logdet = np.linalg.slogdet(A)
+    logdet = logdet if sign > 0 else np.nan
+    half_ulp = 0.5 * float(np.spacing(np.float32(abs(logdet)))) if np.isfinite(logdet) else 0.0
+    return {"X": X, "d": d, "growth": G.max() / np.abs(A).max(), "logdet": logdet, "sum_term": sum_term(d),
+            "inv_unit": U32 * np.linalg.norm(aX @ np.abs(A) @ aX) / np.linalg.norm(X), "ld_bound": U32 * np.sum(aX * G) + sum_term(d) + half_ulp}
+
+
+def hard_reference(kind, D, seed):
+    """reference64 of the matrix the device inverts for hard_matrix(kind, D, seed); once per input, shared and left unchanged."""
+    key = ("ref", kind, D, seed)
+    if key not in _cache:
+        _cache[key] = reference64(inverted(kind, hard_matrix(kind, D, seed)), spd=D > SPD_SHORTCUT_BEYOND and kind in SPD_KINDS + SCALED_KINDS)
+    return _cache[key]
+
+
+def inverse_error(X, ref):
+    """||X - X64||_F / ||X64||_F"""
+    return float(np.linalg.norm(np.asarray(X, dtype=np.float64) - ref["X"]) / np.linalg.norm(ref["X"]))
+
+
+def residual(A, X):
+    """||A X - I||_F / sqrt(D) in fp64"""
+    return float(np.linalg.norm(A @ np.asarray(X, dtype=np.float64) - np.eye(len(A))) / np.sqrt(len(A)))
+
+
+def torch32(A):
+    """(inverse, log-determinant) of the reference's own arithmetic: torch.linalg.inv and torch.logdet on the CPU in fp32 on the fp32 rounding of A."""
+    a = torch.from_numpy(np.asarray(A, dtype=np.float32).copy())
+    return torch.linalg.inv(a).numpy(), float(torch.logdet(a))
