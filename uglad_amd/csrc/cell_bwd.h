@@ -38,9 +38,14 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
   // s slabs (gridDim.x matrices) below.  dL/dZ stays in LDS from one step to the next -- the two big buffers swap roles -- the 28 rhoNN
   // gradient sums stay in registers, and only the last step writes G_out.  k_count = 1 is the per-step entry point.
   const size_t step_mdd = (size_t)gridDim.x * D * D, step_md = (size_t)gridDim.x * D;
+  // The 28 rhoNN gradient sums.  kPackA: phase A runs the rhoNN backward of two entries at a time (rho_backward2) and the sums are kept as
+  // pairs, g2[q].x over a thread's even entries and g2[q].y over its odd ones, added once in front of the final reduction; 28 more registers
+  // across the whole step loop.  NT = 8 (224 VGPRs with the sums held once) keeps them once and the backward entry by entry.
+  constexpr bool kPackA = NT <= 7;
   float g[kNRho];
+  [[maybe_unused]] v2f g2[kNRho];
 #pragma unroll
-  for (int q = 0; q < kNRho; ++q) g[q] = 0.f;
+  for (int q = 0; q < kNRho; ++q) g[q] = 0.f, g2[q] = splat2(0.f);
   // The upper-triangle entries of a thread (entry e = tid + kThreads q, as in the forward cell) are the same in every step.  DP <= 128: they are
   // worked out once, here, into s_ent[q][tid] = (i << 8) | j, 0xffff where there is none ([q][tid]: a wave reads 64 consecutive shorts), and
   // phase A and the G_out assembly of every step read them back in the order q = 0, 1, ... they were walked in -- the summation order of the 28
@@ -189,9 +194,27 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
         }
       }
     }
+    // DP <= 128: phase A's operands from global memory (H, Z, S of every entry of this thread) are requested here, in front of the spectrum
+    // set-up, whose two block sums cost four barriers, and waited for behind it.  Clamped addresses.  The set-up's own operand, beta of this
+    // thread, is requested first: loads return in order, and behind the 51 its wait would be a wait for all of them.
+    const float be_ld = load_at<float>(bm, (tid < D) ? 4u * (unsigned)tid : 0u);
+    [[maybe_unused]] float hx_a[kQ], zz_a[kQ], sv_a[kQ];
+    if constexpr (kPre) {
+      int ea[kQ];
+#pragma unroll
+      for (int u = 0; u < kQ; ++u) ea[u] = (int)(short)s_ent[u][tid];
+#pragma unroll
+      for (int u = 0; u < kQ; ++u) {
+        // (opaque: left visible, the select becomes a branch around the address, behind a wait for this entry's table read alone)
+        const unsigned at = (unsigned)opaque_v((ea[u] >= 0) ? 4 * ((ea[u] >> kIShift) * D + (ea[u] & kJMask)) : 0);
+        hx_a[u] = load_at<float>(Hm, at);
+        zz_a[u] = load_at<float>(Zm, at);
+        sv_a[u] = load_at<float>(Sm, at);
+      }
+    }
     float a2 = 0.f;
     if (tid < D) {
-      const float be = bm[tid];
+      const float be = be_ld;
       const float al = fmaf(be, be, c4);
       a2 = al * al;
     }
@@ -200,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
     if (tid < DP) {
       float be = 0.f, r = 1.f;
       if (tid < D) {
-        be = bm[tid];
+        be = be_ld;
         r = sqrt_spectrum(be, c4, nrmA, mode);
         r2 = r * r;
       }
@@ -228,8 +251,8 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
         int pk[kQ];
         float hx[kQ], zz[kQ], gn[kQ], sv[kQ];
         if constexpr (kPre) {
-          // the pass's indices together, then every operand from a clamped address with the value selected afterwards: 32-bit offsets
-          // (load_at), no branch per entry, the two LDS reads of every G entry issued before the first of them is waited for
+          // the pass's indices together, then every operand from a clamped address (H, Z, S: requested in front of the spectrum set-up), no
+          // branch per entry, the two LDS reads of every G entry issued before the first of them is waited for
 #pragma unroll
           for (int u = 0; u < kQ; ++u) pk[u] = (int)(short)s_ent[u][tid];
           float gt[kQ];
@@ -237,22 +260,16 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
           for (int u = 0; u < kQ; ++u) {
             const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
             const bool in = pk[u] >= 0;
-            const unsigned at = in ? 4u * ((unsigned)i * (unsigned)D + (unsigned)j) : 0u;
-            gz[u] = 0.f;
-            hx[u] = load_at<float>(Hm, at);
-            zz[u] = load_at<float>(Zm, at);
-            sv[u] = load_at<float>(Sm, at);
             gn[u] = sY[opaque_v(in ? i * LD + j : 0)];  // (opaque: left visible, the select becomes a branch around the two reads)
             gt[u] = sY[opaque_v(in ? j * LD + i : 0)];
           }
+          // an entry that does not exist keeps the finite operands of the clamped addresses (entry (0, 0)): below it has g_rho = 0 and weight 0
+          static_assert(kPackA || !kPre, "the tabled entries go with the packed backward");
 #pragma unroll
           for (int u = 0; u < kQ; ++u) {
             const int i = pk[u] >> kIShift, j = pk[u] & kJMask;
-            const bool in = pk[u] >= 0;
-            hx[u] = in ? hx[u] : 0.f;
-            zz[u] = in ? zz[u] : 0.f;
-            sv[u] = in ? sv[u] : 0.f;
-            gn[u] = in ? ((i == j) ? gn[u] : 0.5f * (gn[u] + gt[u])) : 0.f;
+            hx[u] = hx_a[u], zz[u] = zz_a[u], sv[u] = sv_a[u];
+            gn[u] = (i == j) ? gn[u] : 0.5f * (gn[u] + gt[u]);
           }
         } else {
 #pragma unroll
@@ -267,9 +284,62 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
             gn[u] = in ? ((i == j) ? sY[i * LD + j] : 0.5f * (sY[i * LD + j] + sY[j * LD + i])) : 0.f;
           }
         }
-        // forward activations of two entries at a time on the packed fp32 pipe, the backward entry by entry (packed, its 28
-        // accumulators would need a second set of registers that the kernel does not have)
         constexpr int kQ2 = (kQ + 1) / 2;
+        if constexpr (kPackA) {
+          [[maybe_unused]] const int tid_a = opaque_v(tid);
+          // forward activations and backward of two entries at a time on the packed fp32 pipe: rho_backward2 takes the pair as rho_forward2
+          // left it and adds it to the two halves of g2.  No branch per entry: one that does not exist (also the missing partner of the odd
+          // one out) or is inactive has g_rho = 0 and weight 0 and finite operands, so it adds exact zeros to every sum and its gh and gz
+          // are 0; one that does not exist stores its gh to the padding column, which nobody reads.
+#pragma unroll
+          for (int h = 0; h < kQ2; ++h) {
+            const int u0 = 2 * h, u1 = (2 * h + 1 < kQ) ? 2 * h + 1 : 2 * h;
+            const bool has1 = 2 * h + 1 < kQ;
+            // (DP <= 128: the pair's indices from the table again, through tid_a, rather than 17 registers held from the reads above)
+            const int e0 = kPre ? (int)(short)s_ent[kPre ? u0 : 0][kPre ? tid_a : 0] : pk[u0];
+            const int e1 = kPre ? (int)(short)s_ent[kPre ? u1 : 0][kPre ? tid_a : 0] : pk[u1];
+            const bool in0 = e0 >= 0, in1 = has1 && e1 >= 0;
+            const int i0 = e0 >> kIShift, j0 = e0 & kJMask, i1 = e1 >> kIShift, j1 = e1 & kJMask;
+            const v2f x = {hx[u0], has1 ? hx[u1] : 0.f}, s2 = {sv[u0], has1 ? sv[u1] : 0.f}, z2 = {zz[u0], has1 ? zz[u1] : 0.f};
+            const v2f gn2 = {gn[u0], has1 ? gn[u1] : 0.f};
+            RhoAct2 act2;
+            rho_forward2(params, x, s2, z2, act2);
+            const bool on0 = in0 && fabsf(x.x) > act2.rho.x, on1 = in1 && fabsf(x.y) > act2.rho.y;
+            const v2f gact = {on0 ? gn2.x : 0.f, on1 ? gn2.y : 0.f};
+            // -sign(x) g for an active entry (|x| > rho >= 0: x is not 0)
+            const v2f g_rho = {on0 ? ((x.x > 0.f) ? -gn2.x : gn2.x) : 0.f, on1 ? ((x.y > 0.f) ? -gn2.y : gn2.y) : 0.f};
+            const v2f wgt = {on0 ? ((i0 == j0) ? 1.f : 2.f) : 0.f, on1 ? ((i1 == j1) ? 1.f : 2.f) : 0.f};
+            v2f gx1, gx3;
+            rho_backward2(params, x, s2, z2, act2, g_rho, wgt, g2, gx1, gx3);
+            // (opaque: the sums and dL/dZ's direct part exist here, in registers -- left to the compiler, what is only needed behind the four
+            // products is computed there, and its operands, three and more registers per value, are kept or spilled until then)
+#pragma unroll
+            for (int q = 0; q < kNRho; ++q) g2[q] = opaque_f2(g2[q]);
+            gx3 = opaque_f2(gx3);
+#if UGLAD_CELL_BWD_GS
+            // (upper triangle; mirrored with the G_B term at the end of the step)
+            if (in0) gS[base + i0 * D + j0] += rho_backward_col(params, act2.half(0), g_rho.x, 1);
+            if (in1) gS[base + i1 * D + j1] += rho_backward_col(params, act2.half(1), g_rho.y, 1);
+#endif
+            const v2f gh = gact + gx1;
+            // (opaque, as for the reads: left visible, the select becomes a branch around the two stores)
+            sY[opaque_v(in0 ? i0 * LD + j0 : DP)] = gh.x;
+            sY[opaque_v(in0 ? j0 * LD + i0 : DP)] = gh.x;
+            if (has1) {
+              sY[opaque_v(in1 ? i1 * LD + j1 : DP)] = gh.y;
+              sY[opaque_v(in1 ? j1 * LD + i1 : DP)] = gh.y;
+            }
+            if constexpr (kPre) {
+              gz[u0] = gx3.x;
+              if (has1) gz[u1] = gx3.y;
+            } else {
+              if (in0) Go[i0 * D + j0] = gx3.x;
+              if (in1) Go[i1 * D + j1] = gx3.y;
+            }
+          }
+        } else {
+        // forward activations of two entries at a time on the packed fp32 pipe, the backward entry by entry (kPackA: the 28 more
+        // accumulators of the packed form do not fit this instantiation's registers)
 #pragma unroll
         for (int h = 0; h < kQ2; ++h) {
           const int u0 = 2 * h, u1 = (2 * h + 1 < kQ) ? 2 * h + 1 : 2 * h;
@@ -300,6 +370,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
               else Go[i * D + j] = gx3;
             }
           }
+        }
         }
       }
     }
@@ -481,6 +552,7 @@ __global__ __launch_bounds__(kThreads) void UGLAD_CELL_BWD_NAME(
     if (last) {
 #pragma unroll
       for (int q = 0; q < kNRho; ++q) {
+        if constexpr (kPackA) g[q] = g2[q].x + g2[q].y;
         const float v = wave_sum(g[q]);
         if (lane == 0) s_g[w][q] = v;
       }

@@ -170,6 +170,12 @@ __device__ __forceinline__ void rho_forward(const float* __restrict__ p, float x
 // Two entries at a time on the packed fp32 pipe (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: one issue slot for two lanes'
 // worth of work; only exp2 and rcp stay scalar).  Same arithmetic, operation by operation, as the scalar versions above.
 typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2f opaque_f2(v2f v) {  // opaque_f for a pair (one 64-bit register pair)
+#ifndef UGLAD_SIMT_EMUL
+  asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat2(float a) { return (v2f){a, a}; }
 __device__ __forceinline__ v2f exp_acc2(v2f x) {
@@ -278,6 +284,10 @@ __device__ __forceinline__ float rho_backward_col(const float* __restrict__ p, c
 }
 
 // rho_backward for two entries at once (packed fp32 pipe); g2[q].x + g2[q].y is what the scalar version accumulates in g[q].
+// What goes on into dL/dZ -- d/dx1 and d/dx3 and the chain that leads to them -- is written with its fused multiply-adds explicit, in the order
+// in which the entry-by-entry form of cell_bwd.h was evaluated when rho_backward left it to -ffp-contract: which of three products is rounded
+// and which are fused is the last bit of dL/dZ_half, and on an ill-conditioned matrix that bit times the condition number is the error of
+// dL/dlam (tests/test_cell_bwd_entrywise.py, d33_graded).  Stated here, it no longer depends on how a build happens to contract the expression.
 __device__ __forceinline__ void rho_backward2(const float* __restrict__ p, v2f x1, v2f x2, v2f x3, const RhoAct2& a, v2f g_rho,
                                               v2f w, v2f* g2, v2f& gx1, v2f& gx3) {
   const v2f go = g_rho * a.rho * (1.f - a.rho);
@@ -298,7 +308,9 @@ __device__ __forceinline__ void rho_backward2(const float* __restrict__ p, v2f x
   }
 #pragma unroll
   for (int h = 0; h < 3; ++h) {
-    const v2f s = ga2[0] * p[P_RW2 + h] + ga2[1] * p[P_RW2 + 3 + h] + ga2[2] * p[P_RW2 + 6 + h];
+    // (the order of each sum of three products is written out, see above: h = 0 rounds the middle product, h = 1, 2 the first)
+    const v2f s = (h == 0) ? fma2(ga2[2], splat2(p[P_RW2 + 6]), fma2(ga2[0], splat2(p[P_RW2]), ga2[1] * p[P_RW2 + 3]))
+                           : fma2(ga2[2], splat2(p[P_RW2 + 6 + h]), fma2(ga2[1], splat2(p[P_RW2 + 3 + h]), ga2[0] * p[P_RW2 + h]));
     ga1[h] = s * (1.f - a.h1[h] * a.h1[h]);
   }
 #pragma unroll
@@ -309,8 +321,8 @@ __device__ __forceinline__ void rho_backward2(const float* __restrict__ p, v2f x
     g2[(P_RW1 - 1) + 3 * o + 2] = fma2(t, x3, g2[(P_RW1 - 1) + 3 * o + 2]);
     g2[(P_RB1 - 1) + o] += t;
   }
-  gx1 = ga1[0] * p[P_RW1 + 0] + ga1[1] * p[P_RW1 + 3] + ga1[2] * p[P_RW1 + 6];
-  gx3 = ga1[0] * p[P_RW1 + 2] + ga1[1] * p[P_RW1 + 5] + ga1[2] * p[P_RW1 + 8];
+  gx1 = fma2(ga1[2], splat2(p[P_RW1 + 6]), fma2(ga1[0], splat2(p[P_RW1 + 0]), ga1[1] * p[P_RW1 + 3]));
+  gx3 = opaque_f2(ga1[2] * p[P_RW1 + 8]) + fma2(ga1[1], splat2(p[P_RW1 + 5]), ga1[0] * p[P_RW1 + 2]);  // (opaque: the product is rounded, not fused)
 }
 
 // ------------------------------------------------------------------------------------------ LambdaNN (glad_params.py:51-59,83-95)
