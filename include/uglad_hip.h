@@ -435,6 +435,38 @@ int uglad_graph_wide(const float* values, int from_precision, const int* n_keep,
                      int* edge_count, int* edge_ij, float* edge_w, int* degree, int* triangles2, double* stats, int want_stats, int K, int D,
                      float* workspace, uglad_stream_t stream);
 
+/* All eigenvalues of K symmetric matrices, every 1 <= D <= uglad_max_dim(), values only, fp64 throughout, many workgroups per matrix
+ * (csrc/eigvals_wide.h): a blocked Householder tridiagonalisation (panels of 64, the trailing updates on the fp64 MFMA) and Sturm-count
+ * bisection with a fixed number of steps.  A64 (K, D, D) FP64 DEVICE pointer; the matrix solved is its symmetric part (A + A^T) / 2.
+ *   eig_out (K, D)       the eigenvalues, ASCENDING
+ *   summary_out (K, 6)   min eig, max eig, min |eig|, max |eig|, con = max |eig| / min |eig| (eigen_val_condition_num,
+ *                        prepare_data.py:310-325), and the number of eigenvalues < th, as a double
+ * A matrix with a NaN or Inf entry comes back as NaN in all D places (its count is 0); the others of the batch are not touched.  Results
+ * are bit-reproducible and do not depend on K or on the matrix's place in the batch.  One chain of 2 D + D / 64 + 3 launches, no host
+ * readback.  workspace: uglad_eigvalsh_wide_workspace_floats(K, D) floats, 8-byte aligned (UGLAD_E_NULL otherwise).  K <= 65535.
+ * UGLAD_E_NULL / UGLAD_E_DIM as for uglad_covariance_wide; the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond
+ * 2^31 - 1 floats. */
+int uglad_eigvalsh_wide_workspace_floats(int K, int D);
+int uglad_eigvalsh_wide(const double* A64, int K, int D, double th, double* eig_out, double* summary_out, float* workspace,
+                        uglad_stream_t stream);
+
+/* The same for the empirical covariance (centred, / N) of K tables X64 (K, N, D) FP64, N >= 1: analyse_condition_number
+ * (prepare_data.py:569-594) without the table leaving the device.  The covariance is formed by the Gram product of
+ * uglad_covariance_wide straight into the solver's slab; cov_out (K, D, D) FP64 or NULL also receives it, exactly symmetric.
+ * workspace: uglad_eigvalsh_wide_workspace_floats(K, D). */
+int uglad_table_spectrum(const double* X64, int K, int N, int D, double th, double* eig_out, double* summary_out, double* cov_out,
+                         float* workspace, uglad_stream_t stream);
+
+/* get_highly_correlated_features (prepare_data.py:519-550) for K covariance matrices S64 (K, D, D) FP64, every 2 <= D <= uglad_max_dim()
+ * (csrc/corr_wide.h): cov2 = the covariance of S's rows (/ D, centred) with a zero diagonal; th = the element at index int(0.1 n) of the
+ * n = D (D - 1) / 2 upper-triangle |cov2| in descending order, found exactly by a radix select on the fp64 bit patterns; counts (K, D)
+ * int32 = the entries of a row of |cov2| that are >= th; order (K, D) int32 = the features by count descending, ties by index ascending;
+ * n_listed (K) int32 = the features with a non-zero count: order[k][:n_listed[k]] is the reference's list.  One chain of 21 launches, no
+ * host readback.  workspace: uglad_correlated_features_workspace_floats(K, D) floats, 8-byte aligned.  Errors as uglad_eigvalsh_wide. */
+int uglad_correlated_features_workspace_floats(int K, int D);
+int uglad_correlated_features(const double* S64, int K, int D, int* order, int* counts, int* n_listed, float* workspace,
+                              uglad_stream_t stream);
+
 /* The same decomposition by two-sided cyclic Jacobi (round-robin ordering, Rutishauser rotations): slower, independent of
  * the divide & conquer solver; beta comes back unsorted.  Cross-check only. */
 int uglad_symeig_jacobi(const float* A, float* U, float* beta, int M, int D, uglad_stream_t stream);

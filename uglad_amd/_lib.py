@@ -84,6 +84,14 @@ _SIGS = {
     "uglad_graph_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_graph_wide": ([_c_float_p, ctypes.c_int, ctypes.c_void_p, _c_float_p] + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          _c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_eigvalsh_wide_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_eigvalsh_wide": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, _c_float_p,
+                             ctypes.c_void_p], ctypes.c_int),
+    "uglad_table_spectrum": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3
+                             + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_correlated_features_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_correlated_features": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3 + [_c_float_p, ctypes.c_void_p],
+                                  ctypes.c_int),
     "uglad_set_wide_mode": ([ctypes.c_int], ctypes.c_int),
     "uglad_glad_backward_wrt_s": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + [_c_float_p] * 13
                                   + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
@@ -438,6 +446,48 @@ class HipLib:
         self._call("uglad_sample_scores", self._vp(X64), int(xb), self._vp(P64), self._vp(mean64), self._vp(maha), self._vp(dens),
                    self._vp(logdet), self._p(wsp), K, N, D)
         return maha, dens, logdet
+
+    def eigvalsh_wide(self, A64, th: float = 0.0):
+        """uglad_eigvalsh_wide, every D <= max_dim: (K,D,D) FLOAT64 matrices -> (eig (K,D) float64 ASCENDING, summary (K,6) float64: min,
+        max, min |.|, max |.|, con = max |.| / min |.|, the number of eigenvalues < th), on the device.  The symmetric part is what is
+        solved; a matrix with a non-finite entry comes back as NaN in all places (csrc/eigvals_wide.h)."""
+        self._require_f64(A64, 3, "eigvalsh_wide takes a contiguous (K, D, D) float64 tensor")
+        K, D, D2 = A64.shape
+        if D2 != D:
+            raise UgladError("eigvalsh_wide takes a contiguous (K, D, D) float64 tensor")
+        wsp = self._wide_workspace("uglad_eigvalsh_wide", A64.device, K, D)
+        eig = torch.empty(K, D, dtype=torch.float64, device=A64.device)
+        summary = torch.empty(K, 6, dtype=torch.float64, device=A64.device)
+        self._call("uglad_eigvalsh_wide", self._vp(A64), K, D, float(th), self._vp(eig), self._vp(summary), self._p(wsp))
+        return eig, summary
+
+    def table_spectrum(self, X64, th: float = 0.0, want_cov: bool = False):
+        """uglad_table_spectrum: (K,N,D) FLOAT64 tables -> (eig, summary, cov) of their empirical covariances (centred, / N) as
+        eigvalsh_wide returns them; cov (K,D,D) float64 with `want_cov`, else None."""
+        self._require_f64(X64, 3, "table_spectrum takes a contiguous (K, N, D) float64 tensor")
+        K, N, D = X64.shape
+        dev = X64.device
+        wsp = self._wide_workspace("uglad_eigvalsh_wide", dev, K, D)
+        eig = torch.empty(K, D, dtype=torch.float64, device=dev)
+        summary = torch.empty(K, 6, dtype=torch.float64, device=dev)
+        cov = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_cov else None
+        self._call("uglad_table_spectrum", self._vp(X64), K, N, D, float(th), self._vp(eig), self._vp(summary), self._vp(cov), self._p(wsp))
+        return eig, summary, cov
+
+    def correlated_features(self, S64):
+        """uglad_correlated_features, every 2 <= D <= max_dim: (K,D,D) FLOAT64 covariance matrices -> (order (K,D), counts (K,D),
+        n_listed (K)) int32 on the device: order[k][:n_listed[k]] is get_highly_correlated_features of matrix k (csrc/corr_wide.h)."""
+        self._require_f64(S64, 3, "correlated_features takes a contiguous (K, D, D) float64 tensor")
+        K, D, D2 = S64.shape
+        if D2 != D:
+            raise UgladError("correlated_features takes a contiguous (K, D, D) float64 tensor")
+        dev = S64.device
+        wsp = self._wide_workspace("uglad_correlated_features", dev, K, D)
+        order = torch.empty(K, D, dtype=torch.int32, device=dev)
+        counts = torch.empty(K, D, dtype=torch.int32, device=dev)
+        n_listed = torch.empty(K, dtype=torch.int32, device=dev)
+        self._call("uglad_correlated_features", self._vp(S64), K, D, self._vp(order), self._vp(counts), self._vp(n_listed), self._p(wsp))
+        return order, counts, n_listed
 
     def partial_correlations(self, precision):
         K, D, _ = precision.shape

@@ -48,6 +48,8 @@ namespace uglad {
 #include "sort_wide.h"
 #include "metrics_wide.h"
 #include "graph_wide.h"
+#include "eigvals_wide.h"
+#include "corr_wide.h"
 #endif
 #include "theta0.h"
 #include "loss.h"

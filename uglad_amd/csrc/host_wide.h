@@ -41,7 +41,77 @@ static void launch_sortw(hipStream_t st, int K, const SortwView& v) {
   }
 }
 
+// the eigenvalues of K slabs that eigw_prepare_kernel or eigw_gram_kernel has filled (eigvals_wide.h): per column the finish of the one
+// before and its own reflector, then the strip partials of A v; behind every whole panel the trailing update; bisection; summary
+static void launch_eigw(hipStream_t st, int K, int D, double th, const EigwView& v, double* eig_out, double* summary_out) {
+  const int nt = v.DP / kT64, nc = (v.DP + kEigwChunk - 1) / kEigwChunk;
+  const dim3 slabs(K), wg(kWThreads);
+  for (int j = 0; j < D; ++j) {
+    if (j > 0 && j % kEigwPanel == 0) {
+      hipLaunchKernelGGL(eigw_column_kernel, slabs, wg, 0, st, j - 1, -1, D, v);
+      const int T = nt - j / kT64;
+      hipLaunchKernelGGL(eigw_update_kernel, dim3(T, T, K), wg, 0, st, j - kEigwPanel, v);
+      hipLaunchKernelGGL(eigw_column_kernel, slabs, wg, 0, st, -1, j, D, v);
+    } else {
+      hipLaunchKernelGGL(eigw_column_kernel, slabs, wg, 0, st, j - 1, j, D, v);
+    }
+    if (j <= D - 2) hipLaunchKernelGGL(eigw_matvec_kernel, dim3(nc - (j + 1) / kEigwChunk, nt - (j + 1) / kT64, K), wg, 0, st, j, v);
+  }
+  hipLaunchKernelGGL(eigw_bisect_kernel, dim3((D + kWThreads - 1) / kWThreads, K), wg, 0, st, D, v, eig_out);
+  hipLaunchKernelGGL(eigw_summary_kernel, slabs, wg, 0, st, D, th, eig_out, summary_out);
+}
+
 extern "C" {
+
+int uglad_eigvalsh_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, eigw_slab_floats); }
+
+int uglad_eigvalsh_wide(const double* A64, int K, int D, double th, double* eig_out, double* summary_out, float* workspace,
+                        uglad_stream_t stream) {
+  if (!A64 || !eig_out || !summary_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_eigvalsh_wide_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const EigwView v = eigw_view(workspace, D);
+  const int nt = v.DP / kT64;
+  hipLaunchKernelGGL(eigw_prepare_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, A64, D, v);
+  launch_eigw(st, K, D, th, v, eig_out, summary_out);
+  return launch_status();
+}
+
+int uglad_table_spectrum(const double* X64, int K, int N, int D, double th, double* eig_out, double* summary_out, double* cov_out,
+                         float* workspace, uglad_stream_t stream) {
+  if (!X64 || !eig_out || !summary_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_eigvalsh_wide_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const EigwView v = eigw_view(workspace, D);
+  const int nt = v.DP / kT64;
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X64, N, D, 0, v.chol());
+  hipLaunchKernelGGL(eigw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X64, N, D, v, cov_out);
+  launch_eigw(st, K, D, th, v, eig_out, summary_out);
+  return launch_status();
+}
+
+int uglad_correlated_features_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 2, eigw_slab_floats); }
+
+int uglad_correlated_features(const double* S64, int K, int D, int* order, int* counts, int* n_listed, float* workspace,
+                              uglad_stream_t stream) {
+  if (!S64 || !order || !counts || !n_listed || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_correlated_features_workspace_floats(K, D) < 0) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const EigwView v = eigw_view(workspace, D);
+  const int nt = v.DP / kT64;
+  const dim3 tiles(nt, nt, K), wg(kWThreads);
+  const double n = (double)D * (double)(D - 1) / 2.0;
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), wg, 0, st, S64, D, D, 0, v.chol());
+  hipLaunchKernelGGL(eigw_gram_kernel, tiles, wg, 0, st, S64, D, D, v, (double*)nullptr);
+  hipLaunchKernelGGL(corrw_init_kernel, dim3(K), wg, 0, st, (int)(0.1 * n), v);  // (the reference's int(0.1 * len))
+  for (int pass = 0; pass < kCorrwPasses; ++pass) {
+    hipLaunchKernelGGL(corrw_hist_kernel, tiles, wg, 0, st, pass, D, v);
+    hipLaunchKernelGGL(corrw_narrow_kernel, dim3(K), wg, 0, st, pass, v);
+  }
+  hipLaunchKernelGGL(corrw_count_kernel, dim3(D, K), wg, 0, st, D, v, counts);
+  hipLaunchKernelGGL(corrw_order_kernel, dim3(K), wg, 0, st, D, (const int*)counts, order, n_listed);
+  return launch_status();
+}
 
 int uglad_covariance_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, covw_table_floats); }
 

@@ -34,6 +34,7 @@ __all__ = [
     "process_table",
     "analyse_condition_number",
     "get_highly_correlated_features",
+    "eigvalsh_device",
     "synthetic_covariance_batch",
     "cramers_v",
     "correlation_ratio",
@@ -175,17 +176,74 @@ def normalize_table(df, typeN: str):
     return df
 
 
-def analyse_condition_number(table, MESSAGE: str = "", VERBOSE: bool = True):
-    """Covariance, eigenvalues and condition number of a table (ref :569-594)."""
-    S = empirical_covariance(np.asarray(table, dtype=np.float64), assume_centered=False)
-    eig, con = eigen_val_condition_num(S)
+# The device path of the three functions below (device=True): the covariance, ALL its eigenvalues and the ranking of correlated features
+# come from the library (csrc/eigvals_wide.h, csrc/corr_wide.h; every D <= max_dim = 2048), the table is uploaded once as float64 and only
+# a handful of numbers come back per round.  Nothing falls back to the host silently: a table the device cannot take raises UgladError.
+def _device_lib(D: int, what: str):
+    from .. import _lib
+
+    lib = _lib.get_lib()
+    if D < 1 or D > lib.max_dim:
+        raise _lib.UgladError(f"{what}(device=True): {D} columns; the device path covers 1 <= D <= max_dim = {lib.max_dim}")
+    return lib, _lib.device()
+
+
+def _to_device_f64(a, dev) -> torch.Tensor:
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.float64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+
+def eigvalsh_device(A, th: float = 0.0, return_summary: bool = False):
+    """All eigenvalues of the symmetric part of A, (D, D) or (K, D, D), D <= max_dim, in float64 on the device (uglad_eigvalsh_wide),
+    ASCENDING.  A numpy array comes back as a numpy array, a tensor as a tensor on the device.  With `return_summary` also the (.., 6)
+    array min, max, min |.|, max |.|, con = max |.| / min |.|, number of eigenvalues < th."""
+    if np.ndim(A) not in (2, 3) or np.shape(A)[-1] != np.shape(A)[-2]:
+        raise ValueError(f"eigvalsh_device takes (D, D) or (K, D, D); got {tuple(np.shape(A))}")
+    lib, dev = _device_lib(int(np.shape(A)[-1]), "eigvalsh_device")
+    Ad = _to_device_f64(A, dev)
+    single = Ad.dim() == 2
+    eig, summary = lib.eigvalsh_wide(Ad[None] if single else Ad, th=th)
+    if single:
+        eig, summary = eig[0], summary[0]
+    if not torch.is_tensor(A):
+        eig, summary = eig.cpu().numpy(), summary.cpu().numpy()
+    return (eig, summary) if return_summary else eig
+
+
+def _table_spectrum_device(Xd, eigval_th: float, want_cov: bool):
+    """One uglad_table_spectrum call on the (N, D) device table: (eig tensor (D,), con, number of eigenvalues < eigval_th, cov (D, D))."""
+    lib, _ = _device_lib(int(Xd.shape[1]), "analyse_condition_number")
+    eig, summary, cov = lib.table_spectrum(Xd[None], th=eigval_th, want_cov=want_cov)
+    back = summary[0, 4:6].cpu().numpy()  # the readback: con and the count
+    return eig[0], float(back[0]), int(back[1]), (None if cov is None else cov[0])
+
+
+def analyse_condition_number(table, MESSAGE: str = "", VERBOSE: bool = True, device: bool = False):
+    """Covariance, eigenvalues and condition number of a table (ref :569-594).  With ``device=True`` all three come from the device
+    (uglad_table_spectrum, fp64): the eigenvalues are then ASCENDING, where LAPACK's general solver on the host returns them in no
+    particular order -- nothing in the package depends on the order."""
+    if device:
+        X = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+        _, dev = _device_lib(int(X.shape[1]) if X.ndim == 2 else 0, "analyse_condition_number")
+        eig_d, con, _, cov = _table_spectrum_device(_to_device_f64(X, dev), 0.0, True)
+        S, eig = cov.cpu().numpy(), [float(x) for x in eig_d.cpu().numpy()]
+    else:
+        S = empirical_covariance(np.asarray(table, dtype=np.float64), assume_centered=False)
+        eig, con = eigen_val_condition_num(S)
     if VERBOSE:
         print(f"{MESSAGE} covariance matrix: condition number {con}, min eig {min(eig)} max eig {max(eig)}")
     return S, eig, con
 
 
-def get_highly_correlated_features(input_cov: np.ndarray) -> np.ndarray:
-    """Rank features by how many top-10% |cov-of-cov| partners they have (ref :519-550)."""
+def get_highly_correlated_features(input_cov: np.ndarray, device: bool = False) -> np.ndarray:
+    """Rank features by how many top-10% |cov-of-cov| partners they have (ref :519-550).  ``device=True``: the same list from
+    uglad_correlated_features (the threshold by an exact radix select on the fp64 magnitudes; ties by index ascending, which is what the
+    reference's dict insertion order under its stable sort amounts to)."""
+    if device:
+        lib, dev = _device_lib(int(np.shape(input_cov)[-1]), "get_highly_correlated_features")
+        order, _, n_listed = lib.correlated_features(_to_device_f64(input_cov, dev)[None])
+        return order[0, : int(n_listed[0])].cpu().numpy().astype(np.int64)
     cov2 = empirical_covariance(input_cov)
     np.fill_diagonal(cov2, 0.0)
     a = np.abs(cov2)
@@ -206,12 +264,20 @@ def process_table(
     COND_NUM: float = np.inf,
     eigval_th: float = 1e-3,
     VERBOSE: bool = True,
+    device: bool = False,
+    rounds: Optional[list] = None,
 ):
     """Make a real-valued table fit for sparse graph recovery (ref :361-516), in the
     reference's order: drop all-zero rows, fill NaN with the column mean, drop
     single-valued columns, normalise, drop duplicate columns, drop low-variance columns,
     then (only when ``COND_NUM`` is finite) drop highly correlated columns until the
-    covariance condition number is acceptable.  Returns a pandas DataFrame."""
+    covariance condition number is acceptable.  Returns a pandas DataFrame.
+
+    ``device=True`` runs the conditioning loop with the table resident on the device: the pandas steps stay on the host, the cleaned
+    table is uploaded once as float64, and every round costs one uglad_table_spectrum call, one uglad_correlated_features call and the
+    readback of con, the number of eigenvalues below ``eigval_th`` and the indices to drop; columns leave by index_select.  The returned
+    DataFrame is cut from the host table: its values never pass through the device.  More than max_dim = 2048 columns raise UgladError.
+    ``rounds``: a list that receives one ``(columns, con, eigenvalues below eigval_th)`` per covariance analysed from "Processed" on."""
     import pandas as pd
 
     start = time()
@@ -226,7 +292,7 @@ def process_table(
     table = normalize_table(table, NORM)
     if VERBOSE:
         print(f"{msg}: single-valued columns dropped {len(single)}")
-        analyse_condition_number(table, "Input", VERBOSE)
+        analyse_condition_number(table, "Input", VERBOSE, device=device)
     cols = table.columns
     table = table.T.drop_duplicates().T
     if VERBOSE:
@@ -234,19 +300,55 @@ def process_table(
     var = table.var()
     low = list(var[var < MIN_VARIANCE].index)
     table = table.drop(columns=low)
-    cov_table, eig, con = analyse_condition_number(table, "Processed", VERBOSE)
-    itr = 1
-    while con > COND_NUM:
-        lb = int(np.sum(np.array(eig) < eigval_th))
-        if lb == 0:
-            lb = 1
-        feats = get_highly_correlated_features(cov_table)
-        feats = feats[: min(lb, len(feats))]
-        table = table.drop(columns=table.columns[feats])
-        cov_table, eig, con = analyse_condition_number(table, f"{msg} {itr}: corr dropped", VERBOSE)
-        itr += 1
+    if device:
+        table = _condition_on_device(table, msg, COND_NUM, eigval_th, VERBOSE, rounds)
+    else:
+        cov_table, eig, con = analyse_condition_number(table, "Processed", VERBOSE)
+        if rounds is not None:
+            rounds.append((table.shape[1], con, int(np.sum(np.array(eig) < eigval_th))))
+        itr = 1
+        while con > COND_NUM:
+            lb = int(np.sum(np.array(eig) < eigval_th))
+            if lb == 0:
+                lb = 1
+            feats = get_highly_correlated_features(cov_table)
+            feats = feats[: min(lb, len(feats))]
+            table = table.drop(columns=table.columns[feats])
+            cov_table, eig, con = analyse_condition_number(table, f"{msg} {itr}: corr dropped", VERBOSE)
+            if rounds is not None:
+                rounds.append((table.shape[1], con, int(np.sum(np.array(eig) < eigval_th))))
+            itr += 1
     if VERBOSE:
         print(f"{msg}: processed table {table.shape[0]} x {table.shape[1]} in {np.round(time() - start, 3)} s")
+    return table
+
+
+def _condition_on_device(table, msg, COND_NUM, eigval_th, VERBOSE, rounds):
+    """process_table's loop over the covariance's condition number with the table on the device; returns the host table's kept columns."""
+    lib, dev = _device_lib(int(table.shape[1]), "process_table")
+    X = _to_device_f64(table.to_numpy(dtype=np.float64), dev)  # the one upload
+    finite = bool(np.isfinite(COND_NUM))
+
+    def analyse(X, message):
+        eig, con, below, cov = _table_spectrum_device(X, eigval_th, finite)
+        if VERBOSE:
+            ends = eig[[0, -1]].cpu().numpy()
+            print(f"{message} covariance matrix: condition number {con}, min eig {float(ends[0])} max eig {float(ends[1])}")
+        if rounds is not None:
+            rounds.append((int(X.shape[1]), con, below))
+        return con, below, cov
+
+    con, below, cov = analyse(X, "Processed")
+    itr = 1
+    while con > COND_NUM:
+        lb = below if below > 0 else 1
+        order, _, n_listed = lib.correlated_features(cov[None])
+        feats = order[0, : min(lb, int(n_listed[0]))].cpu().numpy()
+        keep = np.setdiff1d(np.arange(table.shape[1]), feats)
+        table = table.drop(columns=table.columns[feats])
+        X = X.index_select(1, torch.from_numpy(keep).to(dev)).contiguous()
+        con, below, cov = analyse(X, f"{msg} {itr}: corr dropped")
+        itr += 1
     return table
 
 
