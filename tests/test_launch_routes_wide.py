@@ -1,13 +1,16 @@
-"""CPU: which kernels the many-workgroup fp64 utilities launch (csrc/host_wide.h: covariance_wide, association, conditional_mean_wide,
-sample_scores, support_metrics_wide, graph_wide) and what their *_workspace_floats return, pinned against tests/golden/launch_routes_wide.json.
+"""CPU: which kernels the nine many-workgroup fp64 utilities launch (csrc/host_wide.h: covariance_wide, association, conditional_mean_wide,
+sample_scores, support_metrics_wide, graph_wide, eigvalsh_wide, table_spectrum, correlated_features) and what their *_workspace_floats return,
+pinned against tests/golden/launch_routes_wide.json.
 
 The machinery is test_launch_routes.py's: the emulator's launch hook under UGLAD_EMUL_RECORD_ONLY=1 in a worker process, made-up addresses for every
 buffer (one 64 GiB range each, so every workspace offset is part of the record), `short` for the kernel's name, per group of calls the counts, the
 return codes that are not 0 and a SHA-256 of the whole record.  uglad_graph_wide reads n_keep on the host: that one array is real.
 
-The fixture was recorded from the host layer as it stood BEFORE the wide utilities' shared pieces got one owner each (the shift bisection in
-chol_wide.h, the radix sort in sort_wide.h, the entry points in host_wide.h), with `python tests/test_launch_routes_wide.py --record <library>` on a
-build of that commit; it is not to be regenerated for a refactoring.  Two normalisations stand between a record and the fixture, both below:
+The fixture's first six groups were recorded from the host layer as it stood BEFORE the wide utilities' shared pieces got one owner each (the
+shift bisection in chol_wide.h, the radix sort in sort_wide.h, the entry points in host_wide.h), with `python tests/test_launch_routes_wide.py
+--record <library>` on a build of that commit; its last three (eigvalsh_wide, table_spectrum, correlated_features) with `--record <library>
+<group> ...`, which leaves the other groups as they are, on a build of the commit before the centred Gram product (cov_wide.h) and the
+symmetriser (chol_wide.h) got one owner each.  It is not to be regenerated for a refactoring.  Two normalisations stand between a record and the fixture, both below:
 RENAMED (a kernel that moved to its owner under a new name -> the name it was recorded under) and a by-value struct argument's size `{n}` -> `{}`
 (a view that holds less than the one it was cut from is a smaller argument; what the kernels read of it is pinned by their results)."""
 import ctypes
@@ -33,6 +36,8 @@ RENAMED = {  # the kernel as it is now -> as the fixture names it
     "uglad::sortw_hist_kernel": "uglad::mw_hist_kernel",
     "uglad::sortw_scan_kernel": "uglad::mw_scan_kernel",
     "uglad::sortw_scatter_kernel": "uglad::mw_scatter_kernel",
+    "uglad::covw_gram_kernel<uglad::CovwSink>": "uglad::covw_gram_kernel",
+    "uglad::covw_gram_kernel<uglad::EigwGramSink>": "uglad::eigw_gram_kernel",
 }
 STRUCT_SIZE = re.compile(r"\{\d+\}")
 
@@ -47,15 +52,19 @@ CT = dict(tlr.CT, d=ctypes.c_double)
 SIGS = {  # (the stream, last, is added by the recorder)
     "uglad_covariance_wide": "piiiidppp", "uglad_association": "piii" + "p" * 5 + "id" + "pppp", "uglad_conditional_mean_wide": "p" * 8 + "iii",
     "uglad_sample_scores": "pi" + "p" * 6 + "iii", "uglad_support_metrics_wide": "ppppiii", "uglad_graph_wide": "pipp" + "p" * 7 + "iiip",
+    "uglad_eigvalsh_wide": "piidppp", "uglad_table_spectrum": "piiidpppp", "uglad_correlated_features": "piipppp",
 }
 SIZES = {"uglad_covariance_wide": 2, "uglad_association": 3, "uglad_conditional_mean_wide": 2, "uglad_sample_scores": 3,
-         "uglad_support_metrics_wide": 2, "uglad_graph_wide": 2}  # arguments of <name>_workspace_floats
+         "uglad_support_metrics_wide": 2, "uglad_graph_wide": 2, "uglad_eigvalsh_wide": 2, "uglad_correlated_features": 2}
+# (arguments of <name>_workspace_floats; uglad_table_spectrum takes uglad_eigvalsh_wide's workspace)
 COV = [(1, 1), (2, 40), (1, 64), (1, 65), (3, 129)]          # (K, D): one tile, ragged, exactly one tile, two tiles, a batch of three tiles
 ASSOC = [(2, 12, 64), (1, 40, 128)]                          # (K, D, W)
 AFTER = [(2, 40), (1, 129)]
 SCORES = [(2, 1, 1), (2, 100, 70), (1, 257, 129)]            # (K, N, D)
 METRICS = [(2, 2), (1, 70), (1, 129)]
 GRAPH = [(2, 2), (2, 70), (65, 40)]                          # (65 problems: two threshold launches)
+EIGVALS = COV                                                # (also table_spectrum's)
+CORR = [(1, 2)] + COV[1:]
 UNALIGNED = ((tlr.BUFFERS.index("ws") + 1) << 36) + 4
 
 
@@ -66,8 +75,9 @@ class Recorder(tlr.Recorder):
             fn = getattr(self.dll, name)
             fn.argtypes = [CT[c] for c in sig] + [ctypes.c_void_p]
             fn.restype = ctypes.c_int
+        for name, n in SIZES.items():
             size = getattr(self.dll, name + "_workspace_floats")
-            size.argtypes, size.restype = [ctypes.c_int] * SIZES[name], ctypes.c_int
+            size.argtypes, size.restype = [ctypes.c_int] * n, ctypes.c_int
         self.keep = []  # the host arrays handed in
 
     def call(self, key, name, *args):
@@ -101,6 +111,15 @@ class Recorder(tlr.Recorder):
     def graph(self, key, K, D, keep, th_in="lam", want_stats=1, from_precision=1, values="a", tri="gt", stats="grad", ws="ws"):
         self.call(f"uglad_graph_wide {key}", "uglad_graph_wide", values, from_precision, self.host_ints(keep) if keep is not None else None, th_in,
                   "lam_in", "b", "c", "d", "U", tri, stats, want_stats, K, D, ws)
+
+    def eigvals(self, key, K, D, A="a", eig="b", summary="c", ws="ws"):
+        self.call(f"uglad_eigvalsh_wide {key}", "uglad_eigvalsh_wide", A, K, D, 0.25, eig, summary, ws)
+
+    def spectrum(self, key, K, D, N=30, X="X", eig="b", summary="c", cov="Z", ws="ws"):
+        self.call(f"uglad_table_spectrum {key}", "uglad_table_spectrum", X, K, N, D, 0.25, eig, summary, cov, ws)
+
+    def corr(self, key, K, D, S="a", order="b", counts="c", n_listed="d", ws="ws"):
+        self.call(f"uglad_correlated_features {key}", "uglad_correlated_features", S, K, D, order, counts, n_listed, ws)
 
     def everything(self):
         for name, n in SIZES.items():  # the numbers: every shape below, and the ends of every range
@@ -145,6 +164,14 @@ class Recorder(tlr.Recorder):
                 self.graph(f"K{K} D{D} given stats{stats}", K, D, [-1] * K, want_stats=stats, from_precision=0)
                 self.graph(f"K{K} D{D} mixed stats{stats}", K, D, mixed, want_stats=stats)
             self.graph(f"K{K} D{D} ranked no stats buffers", K, D, ranked, th_in=None, want_stats=0, tri=None, stats=None)
+        for K, D in EIGVALS:
+            self.size("uglad_eigvalsh_wide", K, D)
+            self.eigvals(f"K{K} D{D}", K, D)
+            self.spectrum(f"K{K} D{D} cov", K, D)
+            self.spectrum(f"K{K} D{D} no cov", K, D, cov=None)
+        for K, D in CORR:
+            self.size("uglad_correlated_features", K, D)
+            self.corr(f"K{K} D{D}", K, D)
         self.refusals()
 
     def refusals(self):
@@ -158,6 +185,9 @@ class Recorder(tlr.Recorder):
                 self.scores(tag, K, 10, D, 1)
                 self.metrics(tag, K, D)
                 self.graph(tag, K, D, [0] * max(K, 1) if K < 65536 else [0])
+                self.eigvals(tag, K, D)
+                self.spectrum(tag, K, D)
+                self.corr(tag, K, D)
                 continue
             self.covariance(tag + " null X", K, D, X=None)
             self.covariance(tag + " null S", K, D, S=None)
@@ -194,6 +224,17 @@ class Recorder(tlr.Recorder):
             self.graph(tag + " n_keep past E", K, D, [D * (D - 1) // 2 + 1])
             self.graph(tag + " n_keep -2", K, D, [-2])
             self.graph(tag + " given without thresholds", K, D, [-1], th_in=None)
+            for arg in ("A", "eig", "summary", "ws"):
+                self.eigvals(tag + f" null {arg}", K, D, **{arg: None})
+            self.eigvals(tag + " unaligned workspace", K, D, ws=UNALIGNED)
+            for arg in ("X", "eig", "summary", "ws"):
+                self.spectrum(tag + f" null {arg}", K, D, **{arg: None})
+            self.spectrum(tag + " unaligned workspace", K, D, ws=UNALIGNED)
+            self.spectrum(tag + " N0", K, D, N=0)
+            for arg in ("S", "order", "counts", "n_listed", "ws"):
+                self.corr(tag + f" null {arg}", K, D, **{arg: None})
+            self.corr(tag + " unaligned workspace", K, D, ws=UNALIGNED)
+            self.corr(tag + " D1", K, 1)
 
 
 def worker(lib_path):
@@ -232,9 +273,16 @@ if __name__ == "__main__":
         json.dump(worker(sys.argv[2]), sys.stdout)
     elif sys.argv[1] == "--dump":
         json.dump(run(sys.argv[2]), sys.stdout, indent=1)
-    elif sys.argv[1] == "--record":
+    elif sys.argv[1] == "--record":  # <library> [group ...]: the groups named, the fixture's other lines as they are; none named: all
+        new = summarise(run(sys.argv[2]))
+        lines = [f"{json.dumps(g)}: {json.dumps(v)}" for g, v in new.items() if g in sys.argv[3:] or not sys.argv[3:]]
+        if sys.argv[3:]:
+            with open(FIXTURE) as f:
+                kept = [line.strip().rstrip(",") for line in f.read().splitlines()[1:-1]]
+            # (in front: a line that stays, the last one too, stays byte for byte)
+            lines += [line for line in kept if json.loads("{" + line + "}").keys().isdisjoint(sys.argv[3:])]
         with open(FIXTURE, "w") as f:
-            f.write("{\n " + ",\n ".join(f"{json.dumps(g)}: {json.dumps(v)}" for g, v in summarise(run(sys.argv[2])).items()) + "\n}\n")
+            f.write("{\n " + ",\n ".join(lines) + "\n}\n")
     sys.exit(0)
 
 import pytest  # noqa: E402
@@ -262,9 +310,9 @@ def test_the_normalisation_names_only_what_moved():
     assert normalised(line) == "uglad::cholw_update_kernel [1 1 1] [256 1 1] 0 {}"
 
 
-@pytest.mark.parametrize("entry", sorted(SIZES))
+@pytest.mark.parametrize("entry", sorted(SIGS))
 def test_every_wide_call_launches_what_it_launched(record, golden, entry):
-    assert sorted(record) == sorted(golden) == sorted(SIZES)
+    assert sorted(record) == sorted(golden) == sorted(SIGS)
     got, want = record[entry], golden[entry]
     for field in ("workspace_floats", "errors", "calls", "launches_per_call", "launches", "sha256"):  # (the digest last: the others say more)
         assert got[field] == want[field], (f"{entry} / {field}: the record differs from the pinned one; "

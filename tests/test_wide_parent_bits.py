@@ -1,9 +1,11 @@
-"""GPU: the many-workgroup fp64 utilities (csrc/host_wide.h: covariance_wide, association, conditional_mean_wide, sample_scores,
-support_metrics_wide, graph_wide) return what they returned before their shared pieces got one owner each -- the shift bisection and the
-reduction helpers in chol_wide.h, the radix sort in sort_wide.h.
+"""GPU: the nine many-workgroup fp64 utilities (csrc/host_wide.h: covariance_wide, association, conditional_mean_wide, sample_scores,
+support_metrics_wide, graph_wide, eigvalsh_wide, table_spectrum, correlated_features) return what they returned before their shared pieces
+got one owner each -- the shift bisection, the reduction helpers and the symmetriser in chol_wide.h, the radix sort in sort_wide.h, the
+centred Gram product in cov_wide.h.
 
-Through the HipLib wrappers on the cases of wide_cases.py, every output equals golden/wide_parent_bits.npz, recorded on an MI355X from the build
-of the commit before (golden/make_wide_parent_goldens.py): the parent's bits where the parent is finite, NaN exactly where it has NaN (payloads
+Through the HipLib wrappers on the cases of wide_cases.py, every output equals golden/wide_parent_bits.npz (the first six) or
+golden/wide_parent_bits_eigw.npz (the last three), each recorded on an MI355X from the build of the commit before the change that touched its
+entry points (golden/make_wide_parent_goldens.py): the parent's bits where the parent is finite, NaN exactly where it has NaN (payloads
 are not compared); in full for the first case of each entry point, by CRC32 per problem for the others.  Which kernels every call launches is
 pinned on the CPU (test_launch_routes_wide.py)."""
 import os
@@ -16,9 +18,20 @@ import wide_cases as wc
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+class _Goldens:
+    """The golden files as one: `files` and [key], as of one of them."""
+
+    def __init__(self, parts):
+        self.where = {key: part for part in parts for key in part.files}
+        self.files = list(self.where)
+
+    def __getitem__(self, key):
+        return self.where[key][key]
+
+
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(HERE, "golden", "wide_parent_bits.npz"))
+    return _Goldens([np.load(os.path.join(HERE, "golden", name)) for name in wc.GOLDENS])
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
-"""The many-workgroup fp64 utilities (csrc/host_wide.h) on the smallest shapes at which each piece they share can go wrong -- the shift
-bisection and the reductions of chol_wide.h, the radix sort of sort_wide.h: shapes, inputs and the comparison shared by the GPU test
+"""The nine many-workgroup fp64 utilities (csrc/host_wide.h) on the smallest shapes at which each piece they share can go wrong -- the shift
+bisection, the reductions and the symmetriser of chol_wide.h, the radix sort of sort_wide.h, the centred Gram product of cov_wide.h: shapes, inputs and the comparison shared by the GPU test
 (test_wide_parent_bits.py) and the generator of its golden (golden/make_wide_parent_goldens.py).  `lib` is the HipLib under test, `dev` where its
 tensors live.  Inputs come from seeded numpy alone, outputs through the HipLib wrappers.
 
@@ -17,6 +17,14 @@ A CASE is (entry, name, parameters); run(lib, dev, case) returns {output: [one a
   "metrics"  support_metrics_wide on scores with ties, exact zeros (of both signs) and, from D = 70, one NaN.  -> out
   "graph"    graph_wide on the same kind of matrix read as a precision matrix: ranked with n_keep = 0, 1 and E, a given threshold, and ranked
              with the statistics.  -> per run threshold, edge_count, edge_ij, edge_w (the m defined rows), degree, and triangles2, stats
+  "eigvals"  eigvalsh_wide with th = 0.25, inside the spectrum of an indefinite matrix that is asymmetric at 1e-5 (the symmetriser of
+             chol_wide.h).  D = 1: one element; D = 40: one ragged tile; D = 70: column 64 starts a second panel (eigw_update_kernel runs), and
+             matrix 1 holds one NaN -- its slab comes back all NaN, slab 0 untouched; D = 129: two trailing updates, the second ragged.
+             -> eig, summary
+  "spectrum" table_spectrum with the covariance: N = 30 < D = 70, singular, zeros in the spectrum; N = 200, D = 129.  The centred Gram product of
+             cov_wide.h through the eigensolver's sink.  -> eig, summary, cov
+  "corr"     correlated_features.  D = 2: n = 1, rank 0.  D = 40: two pairs of duplicated columns whose entries are the largest, so that the
+             magnitude at the threshold's rank and those around it tie to the bit.  -> order, counts, n_listed
 D = 2: E = 1, one ragged tile of everything; D = 40, 70, 129: one ragged tile of 64, two tiles (E = 2415: two key tiles of 2048, the second
 ragged), three."""
 import zlib
@@ -33,8 +41,16 @@ CASES = [
     ("scores", "K2_N100_D70", dict(K=2, N=100, D=70)), ("scores", "K1_N257_D129", dict(K=1, N=257, D=129)),
     ("metrics", "K2_D2", dict(K=2, D=2)), ("metrics", "K2_D70", dict(K=2, D=70)), ("metrics", "K1_D129", dict(K=1, D=129)),
     ("graph", "K2_D2", dict(K=2, D=2)), ("graph", "K2_D70", dict(K=2, D=70)), ("graph", "K1_D129", dict(K=1, D=129)),
+    ("eigvals", "K1_D1", dict(K=1, D=1)), ("eigvals", "K2_D40", dict(K=2, D=40)), ("eigvals", "K2_D70", dict(K=2, D=70)),
+    ("eigvals", "K1_D129", dict(K=1, D=129)),
+    ("spectrum", "K2_N30_D70", dict(K=2, N=30, D=70)), ("spectrum", "K1_N200_D129", dict(K=1, N=200, D=129)),
+    ("corr", "K2_D2", dict(K=2, D=2)), ("corr", "K2_D40", dict(K=2, D=40)), ("corr", "K1_D129", dict(K=1, D=129)),
 ]
-FULL = {entry: next(n for e, n, _ in CASES if e == entry) for entry in ("cov", "assoc", "after", "scores", "metrics", "graph")}
+# golden file -> the entries it holds: the second one was recorded later, from the parent of the change that gave its three entry points'
+# feeders (the centred Gram product, the symmetriser) one owner each
+GOLDENS = {"wide_parent_bits.npz": ("cov", "assoc", "after", "scores", "metrics", "graph"),
+           "wide_parent_bits_eigw.npz": ("eigvals", "spectrum", "corr")}
+FULL = {entry: next(n for e, n, _ in CASES if e == entry) for entries in GOLDENS.values() for entry in entries}
 
 
 def case_id(case):
@@ -145,6 +161,33 @@ def run(lib, dev, case):
             out[f"{tag}/edge_w"] = [_np(g.edge_w[k, :m[k]]) for k in range(K)]
             if kw["want_stats"]:
                 out.update({f"{tag}/triangles2": _np(g.triangles2), f"{tag}/stats": _np(g.stats)})
+    elif entry == "eigvals":
+        K, D = p["K"], p["D"]
+        G = rng.standard_normal((K, D, D))
+        A = 0.5 * (G + G.transpose(0, 2, 1)) + 1e-5 * rng.standard_normal((K, D, D))  # (asymmetric at 1e-5; indefinite: 0.25 is interior)
+        if D == 70:
+            A[1, 5, 33] = np.nan
+        eig, summary = lib.eigvalsh_wide(_t(A, dev), th=0.25)
+        out = {"eig": _np(eig), "summary": _np(summary)}
+    elif entry == "spectrum":
+        K, N, D = p["K"], p["N"], p["D"]
+        X = rng.standard_normal((K, N, D)) * rng.uniform(0.5, 5.0, D) + rng.uniform(-2, 2, D)
+        eig, summary, cov = lib.table_spectrum(_t(X, dev), th=1.0, want_cov=True)
+        out = {"eig": _np(eig), "summary": _np(summary), "cov": _np(cov)}
+    elif entry == "corr":
+        K, D = p["K"], p["D"]
+        G = rng.standard_normal((K, D, D))
+        S = 0.5 * (G + G.transpose(0, 2, 1))
+        if D == 40:
+            # columns 5 = 3 and 20 = 11, the four of them ten times the others: every entry of cov2 in one of these columns equals its twin
+            # in the duplicate to the bit, and these 150 of the 780 magnitudes are the largest -- the one at rank 78 has an exact tie
+            S[:, :, [3, 11]] *= 10.0
+            S[:, [3, 11], :] *= 10.0
+            for a, b in ((3, 5), (11, 20)):
+                S[:, :, b] = S[:, :, a]
+                S[:, b, :] = S[:, a, :]
+        order, counts, n_listed = lib.correlated_features(_t(S, dev))
+        out = {"order": _np(order), "counts": _np(counts), "n_listed": _np(n_listed)}
     if dev != "cpu":
         torch.cuda.synchronize()
     return {name: v if isinstance(v, list) else _per_problem(v) for name, v in out.items()}

@@ -447,6 +447,11 @@ class HipLib:
                    self._vp(logdet), self._p(wsp), K, N, D)
         return maha, dens, logdet
 
+    def _eigw_buffers(self, K: int, D: int, device):
+        """(workspace, eig (K,D), summary (K,6)) of one uglad_eigvalsh_wide or uglad_table_spectrum call: they share the slab layout."""
+        return (self._wide_workspace("uglad_eigvalsh_wide", device, K, D), torch.empty(K, D, dtype=torch.float64, device=device),
+                torch.empty(K, 6, dtype=torch.float64, device=device))
+
     def eigvalsh_wide(self, A64, th: float = 0.0):
         """uglad_eigvalsh_wide, every D <= max_dim: (K,D,D) FLOAT64 matrices -> (eig (K,D) float64 ASCENDING, summary (K,6) float64: min,
         max, min |.|, max |.|, con = max |.| / min |.|, the number of eigenvalues < th), on the device.  The symmetric part is what is
@@ -455,9 +460,7 @@ class HipLib:
         K, D, D2 = A64.shape
         if D2 != D:
             raise UgladError("eigvalsh_wide takes a contiguous (K, D, D) float64 tensor")
-        wsp = self._wide_workspace("uglad_eigvalsh_wide", A64.device, K, D)
-        eig = torch.empty(K, D, dtype=torch.float64, device=A64.device)
-        summary = torch.empty(K, 6, dtype=torch.float64, device=A64.device)
+        wsp, eig, summary = self._eigw_buffers(K, D, A64.device)
         self._call("uglad_eigvalsh_wide", self._vp(A64), K, D, float(th), self._vp(eig), self._vp(summary), self._p(wsp))
         return eig, summary
 
@@ -467,9 +470,7 @@ class HipLib:
         self._require_f64(X64, 3, "table_spectrum takes a contiguous (K, N, D) float64 tensor")
         K, N, D = X64.shape
         dev = X64.device
-        wsp = self._wide_workspace("uglad_eigvalsh_wide", dev, K, D)
-        eig = torch.empty(K, D, dtype=torch.float64, device=dev)
-        summary = torch.empty(K, 6, dtype=torch.float64, device=dev)
+        wsp, eig, summary = self._eigw_buffers(K, D, dev)
         cov = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_cov else None
         self._call("uglad_table_spectrum", self._vp(X64), K, N, D, float(th), self._vp(eig), self._vp(summary), self._vp(cov), self._p(wsp))
         return eig, summary, cov

@@ -1,10 +1,11 @@
-// What the many-workgroup fp64 utilities stand on (cov_wide.h, assoc_wide.h, after_wide.h, score_wide.h): the 64 x 64 tile layer on
+// What the many-workgroup fp64 utilities stand on (cov_wide.h, assoc_wide.h, after_wide.h, score_wide.h, eigvals_wide.h): the 64 x 64 tile layer on
 // v_mfma_f64_16x16x4_f64, the blocked Cholesky factorisation of a slab that is spread over many workgroups, and the bisection of a slab's
 // smallest eigenvalue on that factorisation.
 //
 // The tile layer (t64_): a workgroup of 256 threads owns one 64 x 64 tile; each of its four waves owns a 32 x 32 quadrant as 2 x 2 accumulators
 // f64x4.  The lane-to-element layout of those accumulators is written down ONCE, in t64_for_each_fragment; t64_zero clears them,
-// t64_tile_product fills them, t64_for_each_element is the plain (row, column) sweep of a tile that goes to or from LDS.
+// t64_tile_product fills them, t64_for_each_element is the plain (row, column) sweep of a tile that goes to or from LDS, and
+// t64_symmetric_part is a tile of (A + A^T) / 2, symmetric to the bit, for the clients that take a matrix as it was fitted.
 //
 // The factorisation (cholw_): A - sigma I = L L^T, blocked left-looking on 64 x 64 tiles, two launches per block column j:
 //   cholw_update_kernel   tile (i, j) = A(i, j) - sigma delta - sum_{p < j} L(i, p) L(j, p)^T for every i >= j (a tile product, k = 64 j)
@@ -70,6 +71,21 @@ __device__ __forceinline__ double t64_sum_waves(double part, double (&s_part)[4]
   s_part[threadIdx.x >> 6][lane] = part;
   __syncthreads();
   return ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+}
+
+// tile (I, J) of (A + A^T) / 2 of a (D, D) fp64 matrix: tiles (I, J) and (J, I) of A go through LDS (zero outside the matrix; one barrier),
+// then f(x, y, value, inside) for every element of the tile as t64_for_each_element deals them; inside: row 64 I + x and column 64 J + y
+// are both < D (value is zero elsewhere).  Called by the whole workgroup, once per kernel.
+template <class F>
+__device__ __forceinline__ void t64_symmetric_part(const double* __restrict__ A, int D, int I, int J, F&& f) {
+  __shared__ double s_a[kT64 * kT64Ldt], s_b[kT64 * kT64Ldt];
+  const int i0 = I * kT64, j0 = J * kT64;
+  t64_for_each_element([&](int a, int b) {
+    s_a[a * kT64Ldt + b] = (i0 + a < D && j0 + b < D) ? A[(size_t)(i0 + a) * D + j0 + b] : 0.0;
+    s_b[a * kT64Ldt + b] = (j0 + a < D && i0 + b < D) ? A[(size_t)(j0 + a) * D + i0 + b] : 0.0;
+  });
+  __syncthreads();
+  t64_for_each_element([&](int x, int y) { f(x, y, 0.5 * (s_a[x * kT64Ldt + y] + s_b[y * kT64Ldt + x]), i0 + x < D && j0 + y < D); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the tile product

@@ -4,7 +4,8 @@
 // the entries of its row of |cov2| that are >= th (the zero diagonal included: it counts when th = 0); features by count descending, ties by
 // index ascending, which is the reference's dict insertion order under its stable sort.
 //
-//   covw_stats_kernel, eigw_gram_kernel   cov2 into the slab of eigvals_wide.h's layout: cov_wide.h's centred Gram product with the D x D
+//   covw_stats_kernel, covw_gram_kernel<EigwGramSink>
+//                                         cov2 into the slab of eigvals_wide.h's layout: cov_wide.h's centred Gram product with the D x D
 //                                         matrix as the table (N = D)
 //   corrw_init_kernel                     the rank wanted, an empty prefix, empty bins
 //   8 x { corrw_hist_kernel, corrw_narrow_kernel }
@@ -26,18 +27,15 @@ namespace uglad {
 constexpr int kCorrwBits = 8, kCorrwBins = 1 << kCorrwBits, kCorrwPasses = 64 / kCorrwBits;
 static_assert(kCorrwBins == kWThreads, "thread = bin");
 
-// the selection's state, in the slab's scratch area R behind the eigensolver's partials and flags (eigvals_wide.h); 8-byte aligned
+// the selection's state, in the slab's scratch area R behind the eigensolver's partials and flags (EigwView::behind_flags); 8-byte aligned
 struct CorrwSel {
   unsigned long long prefix;  // the digits found so far, in place; after the last pass the pattern of th
   int rank;                   // the rank wanted among the elements that share the prefix, from the top
   int pad;
   int bins[kCorrwBins];
 };
-__host__ __device__ inline CorrwSel* corrw_sel(const EigwView& v, int t) {
-  const size_t nt = v.DP / kT64;
-  return reinterpret_cast<CorrwSel*>(v.r(t) + nt * v.DP + nt * nt);  // (nt^2 doubles: more than the nt^2 flags)
-}
-static_assert(sizeof(CorrwSel) <= 8 * 3000, "the state fits R at DP = 64 (4096 doubles, 65 of them taken)");
+static_assert(sizeof(CorrwSel) <= 8 * kEigwSpare, "the state fits what R keeps behind the flags");
+__host__ __device__ inline CorrwSel* corrw_sel(const EigwView& v, int t) { return reinterpret_cast<CorrwSel*>(v.behind_flags(t)); }
 __device__ __forceinline__ unsigned long long corrw_key(double x) {
   const double a = fabs(x);
   unsigned long long key;

@@ -11,9 +11,10 @@
 //   min eig ~ 0.
 //
 //   covw_stats_kernel     per table and block of 64 columns: min, max, mean -> mn, scale, mu (fp64; the semantics of cov_kernel)
-//   covw_gram_kernel      one workgroup per upper 64 x 64 tile: S = Xc^T Xc / N on the fp64 MFMA, the table streaming through LDS centred
-//                         and normalised; writes the fp64 slab S64 (row stride DP = D rounded up to 64, identity in the padding) and the
-//                         fp32 S_out, both triangles (the mirror is a copy: exactly symmetric)
+//   covw_gram_kernel<Sink>   one workgroup per upper 64 x 64 tile: S = Xc^T Xc / N on the fp64 MFMA, the table streaming through LDS
+//                         centred and normalised.  The ONE centred Gram product of the wide utilities: what becomes of an element is its
+//                         Sink's.  CovwSink writes the fp64 slab S64 (row stride DP = D rounded up to 64, identity in the padding) and the
+//                         fp32 S_out, both triangles (the mirror is a copy: exactly symmetric); eigvals_wide.h has the eigensolver's
 //   25 x { cholw_bisect_kernel<CovwBracket>, cholw_update_kernel + cholw_panel_kernel<CholwView> per block column of 64 },
 //   cholw_bisect_kernel<CovwBracket>, cholw_repair_kernel
 //                         the shift bisection of chol_wide.h (launch_cholw_bisection): the test at the threshold and 24 steps, each a
@@ -96,8 +97,14 @@ __global__ __launch_bounds__(kWThreads) void covw_stats_kernel(const double* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------------- covariance
-// grid (DP / 64, DP / 64, K); tiles below the diagonal return.  Ragged N and D are zero-filled AFTER centring.
-__global__ __launch_bounds__(kWThreads) void covw_gram_kernel(const double* __restrict__ X, int N, int D, CholwView v, float* __restrict__ S_out) {
+// grid (DP / 64, DP / 64, K); tiles below the diagonal return.  Ragged N and D are zero-filled AFTER centring.  The statistics are
+// covw_stats_kernel's, in vec3 of v's slab (normalize = 0 wrote mn = 0, scale = 1: the loader's (x - 0) * 1 - mu is x - mu to the bit).
+// Sink (the caller's): the types View (vec3(t) and DP as CholwView has them) and Out; every thread builds its own as Sink{v, out, D};
+//   put(t, i, j, cov, inside)   per element of the upper triangle of the padded matrix, i <= j < DP; cov = S(i, j) where inside (j < D)
+//   finish(t, I, J)             behind the tile's last put, called by the whole workgroup
+template <class Sink>
+__global__ __launch_bounds__(kWThreads) void covw_gram_kernel(const double* __restrict__ X, int N, int D, typename Sink::View v,
+                                                              typename Sink::Out* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) double s_stage[2 * kT64Stage];
   const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z;
   if (I > J) return;  // (uniform per workgroup)
@@ -113,20 +120,35 @@ __global__ __launch_bounds__(kWThreads) void covw_gram_kernel(const double* __re
   t64_tile_product<false>(0, N, [&](int which, int, int n) {
     return (n < N && col[which] < D) ? (Xt[(size_t)n * D + col[which]] - mn[which]) * sc[which] - mu[which] : 0.0;
   }, s_stage, s_stage + kT64Stage, acc);
-  double* S64 = v.a(t);
-  float* So = S_out + (size_t)t * D * D;
+  Sink sink{v, out, D};
   t64_for_each_fragment([&](int a, int c, int r, int row, int cl) {
     const int i = I * kT64 + row, j = J * kT64 + cl;
     if (i > j) return;  // (the diagonal tile: its lower half is the mirror of its upper half)
-    const bool inside = j < D;  // (i <= j)
-    const double val = inside ? acc[a][c][r] / (double)N : (i == j ? 1.0 : 0.0);  // the padding carries the identity
-    S64[(size_t)i * DP + j] = val;
-    if (i != j) S64[(size_t)j * DP + i] = val;
-    if (inside) {
-      So[(size_t)i * D + j] = (float)val;
-      if (i != j) So[(size_t)j * D + i] = (float)val;
-    }
+    sink.put(t, i, j, acc[a][c][r] / (double)N, j < D);  // (i <= j)
   });
+  sink.finish(t, I, J);
 }
+
+// M(i, j) = val and, where asked, its mirror (a copy: exactly symmetric)
+template <class T>
+__device__ __forceinline__ void covw_store(T* M, int ld, int i, int j, T val, bool mirror) {
+  M[(size_t)i * ld + j] = val;
+  if (mirror) M[(size_t)j * ld + i] = val;
+}
+
+// the covariance front-end's: the fp64 slab with the identity in the padding, and the fp32 (K, D, D) output
+struct CovwSink {
+  using View = CholwView;
+  using Out = float;
+  CholwView v;
+  float* S_out;
+  int D;
+  __device__ void put(int t, int i, int j, double cov, bool inside) const {
+    const double val = inside ? cov : (i == j ? 1.0 : 0.0);
+    covw_store(v.a(t), v.DP, i, j, val, i != j);
+    if (inside) covw_store(S_out + (size_t)t * D * D, D, i, j, (float)val, i != j);
+  }
+  __device__ void finish(int, int, int) const {}
+};
 
 }  // namespace uglad

@@ -5,10 +5,11 @@
 //
 // Stage 1, Householder tridiagonalisation Q^T A Q = T in ONE stage, blocked in panels of 64 columns (LAPACK's dsytrd / dlatrd, lower form).
 // Both triangles of A are kept, exactly symmetric, so that "column j" is row j and the matrix-vector product reads whole 64-row strips.
-//   eigw_prepare_kernel   one workgroup per tile: (A + A^T) / 2 into the slab (row stride DP = D rounded up to 64, ZERO in the padding:
-//                         every reflector is zero there, so the padding never takes part) and the tile's "holds a non-finite entry" flag
-//   eigw_gram_kernel      (uglad_table_spectrum) the same slab from a table: cov_wide.h's centred Gram product / N, optionally also written
-//                         out as the (K, D, D) fp64 covariance
+//   eigw_prepare_kernel   one workgroup per tile: (A + A^T) / 2 (chol_wide.h's t64_symmetric_part) into the slab (row stride DP = D
+//                         rounded up to 64, ZERO in the padding: every reflector is zero there, so the padding never takes part) and the
+//                         tile's "holds a non-finite entry" flag
+//   covw_gram_kernel<EigwGramSink>   (uglad_table_spectrum) the same slab from a table: cov_wide.h's centred Gram product / N, optionally
+//                         also written out as the (K, D, D) fp64 covariance
 //   per column j:
 //     eigw_column_kernel  one workgroup per slab.  First it finishes column j - 1: y = the strip partials of A v summed in strip order,
 //                         w = tau (y - tau/2 (y^T v) v).  Then column j: row j with the panel's pending corrections applied
@@ -55,7 +56,8 @@ struct EigwCtl {
 // A slab of the workspace, in DOUBLES (DP = t64_padded(D), nt = DP / 64).  It begins like the factorisation's (CholwView: A, a second DP x DP
 // area, three vectors, a control block of 8), so that cov_wide.h's column statistics serve uglad_table_spectrum unchanged:
 //   A      DP x DP    the matrix, both triangles; tridiagonalised in place
-//   R      DP x DP    scratch: the strip partials of A v (nt x DP), behind them the nt x nt tile flags (ints)
+//   R      DP x DP    scratch: the strip partials of A v (nt x DP), behind them the nt x nt tile flags (ints); from behind_flags(t) on
+//                     it is a client's (corr_wide.h), at least kEigwSpare doubles
 //   vec3   3 DP       (table entry) mn | scale | mu of covw_stats_kernel
 //   EigwCtl   8
 //   V | W  64 x DP each   the panel's reflectors and their w, one per row, zero outside (j, D)
@@ -69,6 +71,7 @@ struct EigwView {
   __host__ __device__ double* a(int t) const { return base + (size_t)t * stride; }
   __host__ __device__ double* r(int t) const { return a(t) + (size_t)DP * DP; }
   __host__ __device__ int* flags(int t) const { return reinterpret_cast<int*>(r(t) + (size_t)(DP / kT64) * DP); }
+  __host__ __device__ double* behind_flags(int t) const { return r(t) + (size_t)(DP / kT64) * DP + (size_t)(DP / kT64) * (DP / kT64); }
   __host__ __device__ double* vec3(int t) const { return r(t) + (size_t)DP * DP; }
   __host__ __device__ EigwCtl* ctl(int t) const { return reinterpret_cast<EigwCtl*>(vec3(t) + 3 * (size_t)DP); }
   __host__ __device__ double* V(int t) const { return vec3(t) + 3 * (size_t)DP + 8; }
@@ -80,6 +83,8 @@ struct EigwView {
   __host__ __device__ CholwView chol() const { return CholwView{base, stride, DP}; }
 };
 static_assert(sizeof(EigwCtl) == 64, "the control block is the factorisation's 8 doubles");
+// the doubles of R from behind_flags(t) on: DP^2 - nt DP - nt^2 (nt^2 doubles cover the nt^2 ints) = nt^2 kEigwSpare, least at nt = 1
+constexpr size_t kEigwSpare = (size_t)kT64 * kT64 - kT64 - 1;
 __host__ __device__ constexpr size_t eigw_slab_doubles(int DP) { return cholw_slab_doubles(DP) + (2 * (size_t)kEigwPanel + 3) * DP + 2 * kEigwPanel; }
 __host__ inline size_t eigw_slab_floats(int D) { return 2 * eigw_slab_doubles(t64_padded(D)); }
 __host__ inline EigwView eigw_view(float* workspace, int D) {
@@ -118,62 +123,40 @@ __device__ __forceinline__ void eigw_raise(bool bad, int* flag, int* flag_mirror
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the slab
-// grid (DP / 64, DP / 64, K): tile (I, J) = (blockIdx.y, blockIdx.x) of (A + A^T) / 2 from tiles (I, J) and (J, I) of the input
+// grid (DP / 64, DP / 64, K): tile (I, J) = (blockIdx.y, blockIdx.x) of (A + A^T) / 2, which is zero in the padding
 __global__ __launch_bounds__(kWThreads) void eigw_prepare_kernel(const double* __restrict__ A_in, int D, EigwView v) {
-  __shared__ double s_a[kT64 * kT64Ldt], s_b[kT64 * kT64Ldt];
   const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z, DP = v.DP, nt = DP / kT64;
-  const int i0 = I * kT64, j0 = J * kT64;
-  const double* Ai = A_in + (size_t)t * D * D;
-  t64_for_each_element([&](int a, int b) {
-    s_a[a * kT64Ldt + b] = (i0 + a < D && j0 + b < D) ? Ai[(size_t)(i0 + a) * D + j0 + b] : 0.0;
-    s_b[a * kT64Ldt + b] = (j0 + a < D && i0 + b < D) ? Ai[(size_t)(j0 + a) * D + i0 + b] : 0.0;
-  });
-  __syncthreads();
   double* A = v.a(t);
   bool bad = false;
-  t64_for_each_element([&](int x, int y) {
-    const double val = 0.5 * (s_a[x * kT64Ldt + y] + s_b[y * kT64Ldt + x]);  // (zero in the padding)
+  t64_symmetric_part(A_in + (size_t)t * D * D, D, I, J, [&](int x, int y, double val, bool) {
     bad = bad || !eigw_finite(val);
-    A[(size_t)(i0 + x) * DP + j0 + y] = val;
+    A[(size_t)(I * kT64 + x) * DP + J * kT64 + y] = val;
   });
   int* f = v.flags(t);
   eigw_raise(bad, f + I * nt + J, f + I * nt + J);
 }
 
-// grid (DP / 64, DP / 64, K); tiles below the diagonal return.  The statistics are covw_stats_kernel's (normalize = 0: mu alone matters).
-// cov_out: (K, D, D) fp64 or NULL
-__global__ __launch_bounds__(kWThreads) void eigw_gram_kernel(const double* __restrict__ X, int N, int D, EigwView v, double* __restrict__ cov_out) {
-  __shared__ __attribute__((aligned(16))) double s_stage[2 * kT64Stage];
-  const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z;
-  if (I > J) return;  // (uniform per workgroup)
-  const int lane = threadIdx.x & 63, DP = v.DP, nt = DP / kT64;
-  const double* Xt = X + (size_t)t * N * D;
-  const double* st = v.vec3(t);
-  const int col[2] = {I * kT64 + lane, J * kT64 + lane};
-  const double mu[2] = {st[2 * DP + col[0]], st[2 * DP + col[1]]};
-  f64x4 acc[2][2];
-  t64_zero(acc);
-  t64_tile_product<false>(0, N, [&](int which, int, int n) { return (n < N && col[which] < D) ? Xt[(size_t)n * D + col[which]] - mu[which] : 0.0; },
-                          s_stage, s_stage + kT64Stage, acc);
-  double* A = v.a(t);
-  double* Co = cov_out ? cov_out + (size_t)t * D * D : nullptr;
-  bool bad = false;
-  t64_for_each_fragment([&](int a, int c, int r, int row, int cl) {
-    const int i = I * kT64 + row, j = J * kT64 + cl;
-    if (i > j) return;  // (the diagonal tile: its lower half is the mirror of its upper half)
-    const bool inside = j < D;  // (i <= j)
-    const double val = inside ? acc[a][c][r] / (double)N : 0.0;
+// covw_gram_kernel's sink for the slab of a table's covariance: zero in the padding, the mirror always written (the diagonal twice), the
+// flags of the tile and of its mirror; cov_out: (K, D, D) fp64 or NULL
+struct EigwGramSink {
+  using View = EigwView;
+  using Out = double;
+  EigwView v;
+  double* cov_out;
+  int D;
+  bool bad = false;  // this thread put a non-finite value
+  __device__ void put(int t, int i, int j, double cov, bool inside) {
+    const double val = inside ? cov : 0.0;
     bad = bad || !eigw_finite(val);
-    A[(size_t)i * DP + j] = val;
-    A[(size_t)j * DP + i] = val;
-    if (inside && Co) {
-      Co[(size_t)i * D + j] = val;
-      Co[(size_t)j * D + i] = val;
-    }
-  });
-  int* f = v.flags(t);
-  eigw_raise(bad, f + I * nt + J, f + J * nt + I);
-}
+    covw_store(v.a(t), v.DP, i, j, val, true);
+    if (inside && cov_out) covw_store(cov_out + (size_t)t * D * D, D, i, j, val, true);
+  }
+  __device__ void finish(int t, int I, int J) const {
+    const int nt = v.DP / kT64;
+    int* f = v.flags(t);
+    eigw_raise(bad, f + I * nt + J, f + J * nt + I);
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- one column
 // grid (K), one workgroup per slab: finishes the reflector of column jprev (>= 0), then starts column j (>= 0)

@@ -41,7 +41,14 @@ static void launch_sortw(hipStream_t st, int K, const SortwView& v) {
   }
 }
 
-// the eigenvalues of K slabs that eigw_prepare_kernel or eigw_gram_kernel has filled (eigvals_wide.h): per column the finish of the one
+// the covariance (centred, / N) of K tables of N rows into the slabs of an EigwView, with their tile flags: the column statistics
+// without normalisation, then the Gram product of cov_wide.h; cov_out: (K, D, D) fp64 or NULL
+static void launch_eigw_gram(hipStream_t st, const double* X64, int K, int N, int D, const EigwView& v, double* cov_out) {
+  const int nt = v.DP / kT64;
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X64, N, D, 0, v.chol());
+  hipLaunchKernelGGL(covw_gram_kernel<EigwGramSink>, dim3(nt, nt, K), dim3(kWThreads), 0, st, X64, N, D, v, cov_out);
+}
+// the eigenvalues of K slabs that eigw_prepare_kernel or launch_eigw_gram has filled (eigvals_wide.h): per column the finish of the one
 // before and its own reflector, then the strip partials of A v; behind every whole panel the trailing update; bisection; summary
 static void launch_eigw(hipStream_t st, int K, int D, double th, const EigwView& v, double* eig_out, double* summary_out) {
   const int nt = v.DP / kT64, nc = (v.DP + kEigwChunk - 1) / kEigwChunk;
@@ -83,9 +90,7 @@ int uglad_table_spectrum(const double* X64, int K, int N, int D, double th, doub
   if (uglad_eigvalsh_wide_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
   hipStream_t st = (hipStream_t)stream;
   const EigwView v = eigw_view(workspace, D);
-  const int nt = v.DP / kT64;
-  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X64, N, D, 0, v.chol());
-  hipLaunchKernelGGL(eigw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X64, N, D, v, cov_out);
+  launch_eigw_gram(st, X64, K, N, D, v, cov_out);
   launch_eigw(st, K, D, th, v, eig_out, summary_out);
   return launch_status();
 }
@@ -101,8 +106,7 @@ int uglad_correlated_features(const double* S64, int K, int D, int* order, int* 
   const int nt = v.DP / kT64;
   const dim3 tiles(nt, nt, K), wg(kWThreads);
   const double n = (double)D * (double)(D - 1) / 2.0;
-  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), wg, 0, st, S64, D, D, 0, v.chol());
-  hipLaunchKernelGGL(eigw_gram_kernel, tiles, wg, 0, st, S64, D, D, v, (double*)nullptr);
+  launch_eigw_gram(st, S64, K, D, D, v, nullptr);
   hipLaunchKernelGGL(corrw_init_kernel, dim3(K), wg, 0, st, (int)(0.1 * n), v);  // (the reference's int(0.1 * len))
   for (int pass = 0; pass < kCorrwPasses; ++pass) {
     hipLaunchKernelGGL(corrw_hist_kernel, tiles, wg, 0, st, pass, D, v);
@@ -124,7 +128,7 @@ int uglad_covariance_wide(const double* X, int K, int N, int D, int normalize, d
   const CholwView v = covw_view(workspace, D);
   const int nt = v.DP / kT64;
   hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, K), dim3(kWThreads), 0, st, X, N, D, normalize, v);
-  hipLaunchKernelGGL(covw_gram_kernel, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, v, S_out);
+  hipLaunchKernelGGL(covw_gram_kernel<CovwSink>, dim3(nt, nt, K), dim3(kWThreads), 0, st, X, N, D, v, S_out);
   if (min_eig_out) launch_cholw_bisection<CovwBracket>(st, K, D, eval_offset, v, S_out, min_eig_out);  // (NULL: no repair)
   return launch_status();
 }

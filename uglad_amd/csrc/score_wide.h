@@ -7,8 +7,8 @@
 //   q = xc^T P xc,   log-density = (logdet P - D log 2 pi - q) / 2.
 //
 //   scorew_prepare_kernel   one workgroup per 64 x 64 tile: P into the factorisation's slab A (row stride DP = D rounded up to 64, identity
-//                           in the padding), tile (I, J) and tile (J, I) of Theta through LDS, so P is symmetric to the bit; the control
-//                           block of the factorisation (sigma = 0, active, not flagged)
+//                           in the padding) by chol_wide.h's t64_symmetric_part, so P is symmetric to the bit; the control block of the
+//                           factorisation (sigma = 0, active, not flagged)
 //   scorew_quad_kernel      grid (ceil(N / 64), DP / 64, K): one workgroup owns 64 rows of the table and one block column J of P.
 //                           acc = sum_{I <= J} w Xc[rows, I] P[I, J] on the fp64 MFMA, k = 0 .. 64 (J + 1), w = 2 for I < J and 1 for I = J
 //                           applied where the P operand is loaded (exact): the symmetry halves the flops.  P[j][.] is contiguous along k,
@@ -52,21 +52,13 @@ struct ScorewIn {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- P and the control block
-// grid (DP / 64, DP / 64, K): tile (I, J) = (blockIdx.y, blockIdx.x) of P from tiles (I, J) and (J, I) of Theta
+// grid (DP / 64, DP / 64, K): tile (I, J) = (blockIdx.y, blockIdx.x) of P, the identity in the padding
 __global__ __launch_bounds__(kWThreads) void scorew_prepare_kernel(const double* __restrict__ theta, int D, AfterwView v) {
-  __shared__ double s_a[kT64 * kT64Ldt], s_b[kT64 * kT64Ldt];
   const int I = blockIdx.y, J = blockIdx.x, t = blockIdx.z, DP = v.c.DP;
-  const int i0 = I * kT64, j0 = J * kT64;
-  const double* Th = theta + (size_t)t * D * D;
-  t64_for_each_element([&](int a, int b) {
-    s_a[a * kT64Ldt + b] = (i0 + a < D && j0 + b < D) ? Th[(size_t)(i0 + a) * D + j0 + b] : 0.0;
-    s_b[a * kT64Ldt + b] = (j0 + a < D && i0 + b < D) ? Th[(size_t)(j0 + a) * D + i0 + b] : 0.0;
-  });
-  __syncthreads();
   double* A = v.c.a(t);
-  t64_for_each_element([&](int x, int y) {
-    const int i = i0 + x, j = j0 + y;
-    A[(size_t)i * DP + j] = (i < D && j < D) ? 0.5 * (s_a[x * kT64Ldt + y] + s_b[y * kT64Ldt + x]) : (i == j ? 1.0 : 0.0);
+  t64_symmetric_part(theta + (size_t)t * D * D, D, I, J, [&](int x, int y, double val, bool inside) {
+    const int i = I * kT64 + x, j = J * kT64 + y;
+    A[(size_t)i * DP + j] = inside ? val : (i == j ? 1.0 : 0.0);
   });
   if (I == 0 && J == 0 && threadIdx.x == 0) v.c.ctl(t)->reset(0.0);
 }
