@@ -266,163 +266,273 @@ __device__ __forceinline__ int secular_root_reg(const float* __restrict__ ds, co
   return it + 1;
 }
 
+// ------------------------------------------------------------------------------------------------ divide & conquer, one merge level
+// A level joins neighbouring blocks of h columns into merges of bs = 2 h.  Its phases -- merged order and z, coupling test, the rare
+// walk that separates equal poles, the store behind a secular root, the Gu-Eisenstat vector, the end of the level -- and its formulas
+// are stated ONCE, here.  Who runs them is an INDEX MAP with two instances: which item (original column in the first phase, sorted
+// position afterwards) a thread owns and whether it owns one, in which slot a merge's scalars (rho, skip, fix, bmax) live, and what
+// orders two phases.
+//   WaveMap<SEG>   merges inside a segment of SEG columns (up to 16 and 32 columns): the business of ONE wave, lane = item of the segment,
+//                  phases ordered by the wave's own instruction stream.  Correct only because no other wave touches the segment's columns
+//                  or its scalar slots between two workgroup barriers.
+//   GroupMap<DP>   merges from 64 columns on: the whole workgroup, thread = item, phases ordered by barriers.
+// The drivers, dc_local and the level loop of dc_tridiagonal_lean, pick the map, the lanes per root and the pole count of the secular
+// solver, and keep what is their own: the forms of the eigenvector update, the hand-over of the last merge.
+template <int SEG>
+struct WaveMap {
+  static constexpr bool kNorms = false;   // the column norms of the update stay inside the wave
+  const int lane, seg, first;             // first scalar slot of the segment
+  // per-merge scalars: slot 4 w + (merge index inside the segment) at SEG = 16 -- the waves are at different levels at the same time, so the
+  // workgroup-wide numbering p / bs of the later levels would collide here
+  __device__ __forceinline__ explicit WaveMap(int sg) : lane(threadIdx.x & 63), seg(SEG * sg), first((SEG / 4) * sg) {}
+  __device__ __forceinline__ int item() const { return seg + lane; }
+  __device__ __forceinline__ bool owns(int n) const { return lane < SEG && seg + lane < n; }
+  __device__ __forceinline__ int root(int lpr) const { return seg + lane / lpr; }  // lpr adjacent lanes share a root (sub = index among them)
+  __device__ __forceinline__ int sub(int lpr) const { return lane % lpr; }
+  __device__ __forceinline__ int slot(int p, int bs) const { return first + (p - seg) / bs; }
+  __device__ __forceinline__ int own_slot() const { return first + lane; }         // the merge this thread walks, the slot it resets
+  __device__ __forceinline__ int own_merge(int bs) const { return seg + lane * bs; }
+  __device__ __forceinline__ bool owns_merge(int bs, int n) const { return lane < SEG / bs && seg + lane * bs < n; }
+  __device__ __forceinline__ bool owns_slot() const { return lane < SEG / 4; }
+  __device__ static __forceinline__ void order() { UGLAD_WAVE_SYNC(); }
+};
+template <int DP>
+struct GroupMap {
+  static constexpr bool kNorms = true;    // column norms are summed across waves in ws.nrm2: cleared with the zhat phase
+  const int tid;
+  __device__ __forceinline__ explicit GroupMap(int t) : tid(t) {}
+  __device__ __forceinline__ int item() const { return tid; }
+  __device__ __forceinline__ bool owns(int n) const { return tid < n; }
+  __device__ __forceinline__ int root(int lpr) const { return tid / lpr; }
+  __device__ __forceinline__ int sub(int lpr) const { return tid % lpr; }
+  __device__ __forceinline__ int slot(int p, int bs) const { return p / bs; }
+  __device__ __forceinline__ int own_slot() const { return tid; }
+  __device__ __forceinline__ int own_merge(int bs) const { return tid * bs; }
+  __device__ __forceinline__ bool owns_merge(int bs, int n) const { return tid * bs < n; }
+  __device__ __forceinline__ bool owns_slot() const { return tid < DP / 2 + 1; }
+  __device__ static __forceinline__ void order() { __syncthreads(); }
+};
+
+// Neighbouring poles closer than this are pushed this far apart (see the header of this file); scale = max(max |d| of the merge, rho).
+__device__ __forceinline__ float pole_gap(float cur, float prev, float scale) {
+  constexpr float kEps = 5.96e-8f;
+  return 4.f * kEps * fmaxf(fabsf(cur), fabsf(prev)) + 1e-10f * scale;
+}
+
+// z, merged order, max |d| per merge (item = original column g)
+template <int DP, class Map>
+__device__ __forceinline__ void merge_order(const float* Q, int n, LeanScratch<DP>& ws, const Map& map, int h) {
+  constexpr int LD = DP + 1;
+  const int bs = 2 * h, g = map.item();
+  if (map.owns(n)) {
+    const int lo = (g / bs) * bs, mid = lo + h;
+    const int hi = (lo + bs < n) ? lo + bs : n;
+    const float dg = ws.d[g];
+    int rank = g - lo;
+    float z = 0.f;
+    if (mid < n) {
+      const float ec = ws.e[mid - 1];
+      if (g < mid) {
+#pragma unroll 4
+        for (int j = mid; j < hi; ++j) rank += (ws.d[j] < dg) ? 1 : 0;
+        z = Q[(mid - 1) * LD + g];
+      } else {
+        rank = g - mid;
+#pragma unroll 4
+        for (int j = lo; j < mid; ++j) rank += (ws.d[j] <= dg) ? 1 : 0;
+        z = (ec >= 0.f) ? Q[mid * LD + g] : -Q[mid * LD + g];
+      }
+      z *= 0.70710678f;
+      if (fabsf(z) < kZFloor) z = (z < 0.f) ? -kZFloor : kZFloor;
+      atomicMax(&ws.bmax[map.slot(g, bs)], __float_as_int(fabsf(dg)));
+    }
+    ws.ds[lo + rank] = dg;
+    ws.zs[lo + rank] = z;
+    ws.perm[lo + rank] = g;
+  }
+}
+
+// coupling test, rz = rho z^2, detection of poles that need separating (item = sorted position p)
+template <int DP, class Map>
+__device__ __forceinline__ void merge_coupling(int n, LeanScratch<DP>& ws, const Map& map, int h) {
+  constexpr float kEps = 5.96e-8f;
+  const int bs = 2 * h, p = map.item();
+  if (map.owns(n)) {
+    const int blk = map.slot(p, bs), lo = (p / bs) * bs, mid = lo + h;
+    int skip = 1;
+    float rho = 0.f;
+    if (mid < n) {
+      rho = 2.f * fabsf(ws.e[mid - 1]);
+      const float scale = fmaxf(__int_as_float(ws.bmax[blk]), rho);
+      // (judged against the whole matrix as well as the merge: see the header of this file.  The gap below keeps the merge's own scale.)
+      if (rho > 8.f * kEps * fmaxf(scale, __int_as_float(ws.tmax))) {
+        skip = 0;
+        const float z = ws.zs[p];
+        ws.zh[p] = rho * z * z;
+        if (p > lo) {
+          const float cur = ws.ds[p], prev = ws.ds[p - 1];
+          if (cur < prev + pole_gap(cur, prev, scale)) ws.fix[blk] = 1;
+        }
+      }
+    }
+    if (p == lo) {
+      ws.rho[blk] = rho;
+      ws.skip[blk] = skip;
+    }
+  }
+}
+
+// rare: one thread per merge walks its poles and pushes equal ones a few ulps apart
+template <int DP, class Map>
+__device__ __forceinline__ void merge_separate(int n, LeanScratch<DP>& ws, const Map& map, int bs) {
+  const int blo = map.own_merge(bs), blk = map.own_slot();
+  if (map.owns_merge(bs, n) && ws.fix[blk]) {
+    const int bhi = (blo + bs < n) ? blo + bs : n;
+    const float scale = fmaxf(__int_as_float(ws.bmax[blk]), ws.rho[blk]);
+    float prev = ws.ds[blo];
+    for (int j = blo + 1; j < bhi; ++j) {
+      float cur = ws.ds[j];
+      const float gap = pole_gap(cur, prev, scale);
+      if (cur < prev + gap) cur = prev + gap;
+      ws.ds[j] = cur;
+      prev = cur;
+    }
+    ws.fix[blk] = 0;
+  }
+}
+
+// The merge [lo, hi) that sorted position p belongs to, and whether it is carried out (not a lone block at the end, not skipped).
+struct MergeSpan {
+  int lo, hi;
+  bool act;
+};
+template <int DP, class Map>
+__device__ __forceinline__ MergeSpan merge_span(const LeanScratch<DP>& ws, const Map& map, int p, int h, int n) {
+  MergeSpan s = {0, 0, false};
+  if (p < n) {
+    const int bs = 2 * h;
+    s.lo = (p / bs) * bs;
+    s.hi = (s.lo + bs < n) ? s.lo + bs : n;
+    s.act = (s.lo + h < n) && (ws.skip[map.slot(p, bs)] == 0);
+  }
+  return s;
+}
+
+// What one lane per root stores behind secular_root_reg (origin pole K of the merge at lo, mu; K = p - lo, mu = 0 where the merge is not
+// carried out), and the evaluation counters of the diagnostic build (scripts/stamp_lean.py).
+template <int DP>
+__device__ __forceinline__ void store_root(LeanScratch<DP>& ws, int p, int lo, int K, float mu, int evals, int lvl) {
+#ifdef UGLAD_STAMPS
+  if (lvl < 14) {
+    atomicMax(reinterpret_cast<int*>(&ws.stamp[80 + lvl]), evals);
+    atomicAdd(reinterpret_cast<int*>(&ws.stamp[80 + lvl]) + 1, evals);
+  }
+#else
+  (void)evals;
+  (void)lvl;
+#endif
+  const float dK = ws.ds[lo + K];
+  ws.dk[p] = dK;
+  ws.mu[p] = mu;
+  ws.lam[p] = dK + mu;
+}
+
+// Factor i of the Gu-Eisenstat zhat_j^2 = prod_i (lam_i - d_j) / (d_i - d_j), lam_i = dk[i] + mu[i]; and zhat_j with the sign of z_j.
+__device__ __forceinline__ float zhat_factor(const float* dk, const float* mu, const float* ds, int i, int j, float dj) {
+  const float num = (dk[i] - dj) + mu[i];
+  const float den = (i == j) ? 1.f : ds[i] - dj;
+  return num * fast_rcp(den);
+}
+__device__ __forceinline__ float signed_zhat(float prod, float z) {
+  const float zhat = sqrtf(fmaxf(prod, 0.f));
+  return (z < 0.f) ? -zhat : zhat;
+}
+
+// Gu-Eisenstat zhat (pole j = p, LPR lanes each), stored with its pole in the ORIGINAL column order for the GEMM's B operand
+template <int LPR, int DP, class Map>
+__device__ __forceinline__ void merge_zhat(int n, LeanScratch<DP>& ws, const Map&, int p, int sub, const MergeSpan& s) {
+  float prod = 1.f;
+  if (s.act) {
+    const float dj = ws.ds[p];
+#pragma unroll 4
+    for (int i = s.lo + sub; i < s.hi; i += LPR) prod *= zhat_factor(ws.dk, ws.mu, ws.ds, i, p, dj);
+  }
+  prod = group_prod<LPR>(prod);
+  if (sub == 0 && p < n) {
+    ws.act[p] = s.act ? 1 : 0;
+    if (Map::kNorms) ws.nrm2[p] = 0.f;
+    if (s.act) {
+      const int g = ws.perm[p];
+      ws.invo[g] = signed_zhat(prod, ws.zs[p]);
+      ws.dso[g] = ws.ds[p];
+    }
+  }
+}
+
+// Entry W'[k][i] of the merge matrix: column i (sorted position: dki, mui, acti, permi = its original column) against original column k
+// (its pole dso_k and signed zhat invo_k).  A column that is not merged stays where it is.  masked: the merge [blo, blo + bs) is smaller
+// than the tile the caller multiplies, and k may lie outside it.
+__device__ __forceinline__ float merge_entry(bool acti, float invo_k, float dso_k, float dki, float mui, int k, int permi, bool masked = false,
+                                             int blo = 0, int bs = 0) {
+  float val = acti ? invo_k * fast_rcp((dso_k - dki) - mui) : ((k == permi) ? 1.f : 0.f);
+  if (masked && (unsigned)(k - blo) >= (unsigned)bs) val = 0.f;
+  return val;
+}
+
+// End of a level: the merged eigenvalues become the next level's d; the slots of bmax are cleared for its atomicMax.
+template <int DP, class Map>
+__device__ __forceinline__ void merge_finish(int n, LeanScratch<DP>& ws, const Map& map) {
+  if (map.owns(n)) ws.d[map.item()] = ws.lam[map.item()];
+  if (map.owns_slot()) ws.bmax[map.own_slot()] = 0;
+}
+
 // ------------------------------------------------------------------------------------------------ divide & conquer, first levels
-// The merges inside a segment of SEG columns are the business of ONE wave: same steps as the workgroup-wide levels below, but
-// ordered by the wave's own instruction stream instead of barriers -- the waves drift apart and fill each other's latencies,
-// and seven workgroup barriers per level disappear.  SEG = 16: h = 2, 4, 8 on all eight waves (segment [16 w, 16 w + 16)),
+// The merges inside a segment of SEG columns are the business of ONE wave (WaveMap): the waves drift apart and fill each other's
+// latencies, and seven workgroup barriers per level disappear.  SEG = 16: h = 2, 4, 8 on all eight waves (segment [16 w, 16 w + 16)),
 // four lanes per root; the eigenvector update of the 16 x 16 diagonal block is one product on v_mfma_f32_16x16x4_f32.
 // SEG = 32: h = 16 on waves 0..3, two lanes per root, the 32 x 32 block on v_mfma_f32_32x32x2_f32.
 template <int NT, int SEG>
 __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScratch<NT * 32>& ws, int h_first, int lvl, int sg) {
   constexpr int DP = NT * 32, LD = DP + 1;
-  constexpr float kEps = 5.96e-8f;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int LPR = 64 / SEG;  // lanes per root
-  const int seg = SEG * sg;          // (sg = wave index; beyond D = 128 a wave takes several segments in turn)
+  const WaveMap<SEG> map(sg);    // (sg = wave index; beyond D = 128 a wave takes several segments in turn)
+  const int lane = map.lane, seg = map.seg;
   if (seg >= n || seg >= DP) return;  // (wave-uniform)
   const int l16 = lane & 15, g4 = lane >> 4;
-  // per-merge scalars (rho, skip, fix, bmax): slot 4 w + (merge index inside the segment) -- the waves are at different levels
-  // at the same time, so the workgroup-wide numbering p / bs of the later levels would collide here
-  auto slot = [&](int p, int bs) { return (SEG / 4) * sg + (p - seg) / bs; };
   for (int h = h_first; h < SEG && h < n; h *= 2, ++lvl) {
     const int bs = 2 * h;
     if (sg == 0) UGLAD_STAMP(ws, 2 + 5 * lvl);
-    {  // z, merged order, max |d| per merge (lane = original column of the segment)
-      const int g = seg + lane;
-      if (lane < SEG && g < n) {
-        const int lo = (g / bs) * bs, mid = lo + h;
-        const int hi = (lo + bs < n) ? lo + bs : n;
-        const float dg = ws.d[g];
-        int rank = g - lo;
-        float z = 0.f;
-        if (mid < n) {
-          const float ec = ws.e[mid - 1];
-          if (g < mid) {
-            for (int j = mid; j < hi; ++j) rank += (ws.d[j] < dg) ? 1 : 0;
-            z = Q[(mid - 1) * LD + g];
-          } else {
-            rank = g - mid;
-            for (int j = lo; j < mid; ++j) rank += (ws.d[j] <= dg) ? 1 : 0;
-            z = (ec >= 0.f) ? Q[mid * LD + g] : -Q[mid * LD + g];
-          }
-          z *= 0.70710678f;
-          if (fabsf(z) < kZFloor) z = (z < 0.f) ? -kZFloor : kZFloor;
-          atomicMax(&ws.bmax[slot(g, bs)], __float_as_int(fabsf(dg)));
-        }
-        ws.ds[lo + rank] = dg;
-        ws.zs[lo + rank] = z;
-        ws.perm[lo + rank] = g;
-      }
-    }
-    UGLAD_WAVE_SYNC();
-    {  // coupling test, rz = rho z^2, poles that need separating (lane = sorted position)
-      const int p = seg + lane;
-      if (lane < SEG && p < n) {
-        const int lo = (p / bs) * bs, mid = lo + h, blk = slot(p, bs);
-        int skip = 1;
-        float rho = 0.f;
-        if (mid < n) {
-          rho = 2.f * fabsf(ws.e[mid - 1]);
-          const float scale = fmaxf(__int_as_float(ws.bmax[blk]), rho);
-          // (judged against the whole matrix as well as the merge: see the header of this file.  The gap below keeps the merge's own scale.)
-          if (rho > 8.f * kEps * fmaxf(scale, __int_as_float(ws.tmax))) {
-            skip = 0;
-            const float z = ws.zs[p];
-            ws.zh[p] = rho * z * z;
-            if (p > lo) {
-              const float cur = ws.ds[p], prev = ws.ds[p - 1];
-              const float gap = 4.f * kEps * fmaxf(fabsf(cur), fabsf(prev)) + 1e-10f * scale;
-              if (cur < prev + gap) ws.fix[blk] = 1;
-            }
-          }
-        }
-        if (p == lo) {
-          ws.rho[blk] = rho;
-          ws.skip[blk] = skip;
-        }
-      }
-    }
-    UGLAD_WAVE_SYNC();
-    {  // rare: one lane per merge walks its poles and pushes equal ones a few ulps apart
-      const int blo = seg + lane * bs, blk = (SEG / 4) * sg + lane;
-      if (lane < SEG / bs && blo < n && ws.fix[blk]) {
-        const int bhi = (blo + bs < n) ? blo + bs : n;
-        const float scale = fmaxf(__int_as_float(ws.bmax[blk]), ws.rho[blk]);
-        float prev = ws.ds[blo];
-        for (int j = blo + 1; j < bhi; ++j) {
-          float cur = ws.ds[j];
-          const float gap = 4.f * kEps * fmaxf(fabsf(cur), fabsf(prev)) + 1e-10f * scale;
-          if (cur < prev + gap) cur = prev + gap;
-          ws.ds[j] = cur;
-          prev = cur;
-        }
-        ws.fix[blk] = 0;
-      }
-    }
-    UGLAD_WAVE_SYNC();
+    merge_order(Q, n, ws, map, h);
+    map.order();
+    merge_coupling(n, ws, map, h);
+    map.order();
+    merge_separate(n, ws, map, bs);
+    map.order();
     if (sg == 0) UGLAD_STAMP(ws, 3 + 5 * lvl);
-    // secular roots: root p = seg + lane / LPR, LPR lanes each
-    const int p = seg + lane / LPR, sub = lane % LPR;
-    int lo = 0, hi = 0;
-    bool act = false;
-    if (p < n) {
-      lo = (p / bs) * bs;
-      hi = (lo + bs < n) ? lo + bs : n;
-      act = (lo + h < n) && (ws.skip[slot(p, bs)] == 0);
-    }
+    // secular roots: root p = seg + lane / LPR, LPR lanes each; the wave keeps the root's merge for the zhat phase
+    const int p = map.root(LPR), sub = map.sub(LPR);
+    const MergeSpan s = merge_span(ws, map, p, h, n);
     {
-      int K = p - lo;
+      int K = p - s.lo;
       float mu = 0.f;
       int evals = 0;
-      if (act) {
-        const float* dsb = ws.ds + lo;
-        const float* zhb = ws.zh + lo;
-        const float rho = ws.rho[slot(p, bs)];
-        if (SEG == 32) evals = secular_root_reg<LPR, 32 / LPR>(dsb, zhb, rho, hi - lo, p - lo, sub, K, mu);
-        else if (bs == 4) evals = secular_root_reg<LPR, (4 + LPR - 1) / LPR>(dsb, zhb, rho, hi - lo, p - lo, sub, K, mu);
-        else if (bs == 8) evals = secular_root_reg<LPR, 8 / LPR>(dsb, zhb, rho, hi - lo, p - lo, sub, K, mu);
-        else evals = secular_root_reg<LPR, 16 / LPR>(dsb, zhb, rho, hi - lo, p - lo, sub, K, mu);
+      if (s.act) {
+        const float* dsb = ws.ds + s.lo;
+        const float* zhb = ws.zh + s.lo;
+        const float rho = ws.rho[map.slot(p, bs)];
+        const int nb = s.hi - s.lo, i = p - s.lo;
+        if (SEG == 32) evals = secular_root_reg<LPR, 32 / LPR>(dsb, zhb, rho, nb, i, sub, K, mu);
+        else if (bs == 4) evals = secular_root_reg<LPR, (4 + LPR - 1) / LPR>(dsb, zhb, rho, nb, i, sub, K, mu);
+        else if (bs == 8) evals = secular_root_reg<LPR, 8 / LPR>(dsb, zhb, rho, nb, i, sub, K, mu);
+        else evals = secular_root_reg<LPR, 16 / LPR>(dsb, zhb, rho, nb, i, sub, K, mu);
       }
-#ifdef UGLAD_STAMPS
-      if (sub == 0 && p < n) {
-        atomicMax(reinterpret_cast<int*>(&ws.stamp[80 + lvl]), evals);
-        atomicAdd(reinterpret_cast<int*>(&ws.stamp[80 + lvl]) + 1, evals);
-      }
-#else
-      (void)evals;
-#endif
-      if (sub == 0 && p < n) {
-        const float dK = ws.ds[lo + K];
-        ws.dk[p] = dK;
-        ws.mu[p] = mu;
-        ws.lam[p] = dK + mu;
-      }
+      if (sub == 0 && p < n) store_root(ws, p, s.lo, K, mu, evals, lvl);
     }
-    UGLAD_WAVE_SYNC();
+    map.order();
     if (sg == 0) UGLAD_STAMP(ws, 4 + 5 * lvl);
-    {  // Gu-Eisenstat zhat (pole j = p), stored with its pole in the original column order
-      float prod = 1.f;
-      if (act) {
-        const float dj = ws.ds[p];
-        for (int i = lo + sub; i < hi; i += LPR) {
-          const float num = (ws.dk[i] - dj) + ws.mu[i];
-          const float den = (i == p) ? 1.f : ws.ds[i] - dj;
-          prod *= num * fast_rcp(den);
-        }
-      }
-      prod = group_prod<LPR>(prod);
-      if (sub == 0 && p < n) {
-        ws.act[p] = act ? 1 : 0;
-        if (act) {
-          const float zhat = sqrtf(fmaxf(prod, 0.f));
-          const int g = ws.perm[p];
-          ws.invo[g] = (ws.zs[p] < 0.f) ? -zhat : zhat;
-          ws.dso[g] = ws.ds[p];
-        }
-      }
-    }
-    UGLAD_WAVE_SYNC();
+    merge_zhat<LPR>(n, ws, map, p, sub, s);
+    map.order();
     if (sg == 0) UGLAD_STAMP(ws, 5 + 5 * lvl);
     if (SEG == 16) {  // Q(block) <- Q(block) W' diag(1/||.||): C[i][j] = sum_k Q[seg+i][seg+k] W'[seg+k][seg+j], lane group g4: k = 4 g4 + s
       const int col = seg + l16;
@@ -437,8 +547,7 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
       for (int ss = 0; ss < 4; ++ss) {
         const int k = seg + 4 * g4 + ss;
         av[ss] = Q[(seg + l16) * LD + k];
-        float val = acti ? ws.invo[k] * fast_rcp((ws.dso[k] - dki) - mui) : ((k == permi) ? 1.f : 0.f);
-        if ((unsigned)(k - blo) >= (unsigned)bs) val = 0.f;
+        const float val = merge_entry(acti, ws.invo[k], ws.dso[k], dki, mui, k, permi, true, blo, bs);
         bv[ss] = val;
         s2 = fmaf(val, val, s2);
       }
@@ -447,7 +556,7 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
       s2 += __shfl_xor(s2, 16);
       s2 = sum_halves(s2);
       const float sc = acti ? 1.0f / sqrtf(s2) : 1.f;
-      UGLAD_WAVE_SYNC();  // (every lane has read its A operands: the block may be overwritten)
+      map.order();  // (every lane has read its A operands: the block may be overwritten)
 #pragma unroll
       for (int r = 0; r < 4; ++r) Q[(seg + 4 * g4 + r) * LD + col] = acc[r] * sc;
     } else {  // the 32 x 32 block on the 32 x 32 x 2 MFMA: lane half kh takes k = 2 u + kh
@@ -466,8 +575,7 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
       for (int u = 0; u < 16; ++u) {
         const int k = seg + 2 * u + kh;
         av[u] = Q[(seg + li) * LD + k];
-        float val = acti ? ws.invo[k] * fast_rcp((ws.dso[k] - dki) - mui) : ((k == permi) ? 1.f : 0.f);
-        if ((unsigned)(k - blo) >= (unsigned)bs) val = 0.f;
+        const float val = merge_entry(acti, ws.invo[k], ws.dso[k], dki, mui, k, permi, true, blo, bs);
         bv[u] = val;
         s2 = fmaf(val, val, s2);
       }
@@ -475,15 +583,12 @@ __device__ __forceinline__ void dc_local(float* __restrict__ Q, int n, LeanScrat
       for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
       s2 = sum_halves(s2);
       const float sc = acti ? 1.0f / sqrtf(s2) : 1.f;
-      UGLAD_WAVE_SYNC();
+      map.order();
 #pragma unroll
       for (int e = 0; e < 16; ++e) Q[(seg + acc_row(e, lane)) * LD + col] = acc[e] * sc;
     }
-    {
-      if (lane < SEG && seg + lane < n) ws.d[seg + lane] = ws.lam[seg + lane];
-      if (lane < SEG / 4) ws.bmax[(SEG / 4) * sg + lane] = 0;
-    }
-    UGLAD_WAVE_SYNC();
+    merge_finish(n, ws, map);
+    map.order();
     if (sg == 0) UGLAD_STAMP(ws, 6 + 5 * lvl);
   }
 }
@@ -500,7 +605,6 @@ template <int NT>
 __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n, LeanScratch<NT * 32>& ws,
                                                     float* __restrict__ last = nullptr) {
   constexpr int DP = NT * 32, LD = DP + 1;
-  constexpr float kEps = 5.96e-8f;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // the pole loads of secular_root_reg are unconditional and read up to 2 DP - 1 floats past the start of ds / zh (DP = 96, 160: past their
   // end): they have to stay inside the divide & conquer vectors of the scratch, whatever the order of its members becomes
@@ -572,80 +676,17 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
   for (int h = 32; h < n; h *= 2, ++lvl) {
     const int bs = 2 * h;
     // (shadow the outer ones: nothing derived from the thread index is hoisted out of the level loop -- the hoisted values, all of
-    // them one instruction from tid, were what the kernel spilled: profiles/r04_kernel_meta.txt)
+    // them one instruction from tid, were what the kernel spilled: profiles/r04_kernel_meta.txt.  The index map is such a value: it is
+    // built here, inside the body)
     const int tid = opaque_v(threadIdx.x), lane = tid & 63, wv = tid >> 6;
+    const GroupMap<DP> map(tid);
     UGLAD_STAMP(ws, 2 + 5 * lvl);
-    {  // ---- L1: z, merged order, max |d| per merge  (thread g = original column)
-      const int g = tid;
-      if (g < n) {
-        const int lo = (g / bs) * bs, mid = lo + h;
-        const int hi = (lo + bs < n) ? lo + bs : n;
-        const float dg = ws.d[g];
-        int rank = g - lo;
-        float z = 0.f;
-        if (mid < n) {
-          const float ec = ws.e[mid - 1];
-          if (g < mid) {
-#pragma unroll 4
-            for (int j = mid; j < hi; ++j) rank += (ws.d[j] < dg) ? 1 : 0;
-            z = Q[(mid - 1) * LD + g];
-          } else {
-            rank = g - mid;
-#pragma unroll 4
-            for (int j = lo; j < mid; ++j) rank += (ws.d[j] <= dg) ? 1 : 0;
-            z = (ec >= 0.f) ? Q[mid * LD + g] : -Q[mid * LD + g];
-          }
-          z *= 0.70710678f;
-          if (fabsf(z) < kZFloor) z = (z < 0.f) ? -kZFloor : kZFloor;
-          atomicMax(&ws.bmax[g / bs], __float_as_int(fabsf(dg)));
-        }
-        ws.ds[lo + rank] = dg;
-        ws.zs[lo + rank] = z;
-        ws.perm[lo + rank] = g;
-      }
-    }
-    __syncthreads();
-    {  // ---- L2: coupling test, rz = rho z^2, detection of poles that need separating (p = sorted position)
-      const int p = tid;
-      if (p < n) {
-        const int blk = p / bs, lo = blk * bs, mid = lo + h;
-        int skip = 1;
-        float rho = 0.f;
-        if (mid < n) {
-          rho = 2.f * fabsf(ws.e[mid - 1]);
-          const float scale = fmaxf(__int_as_float(ws.bmax[blk]), rho);
-          if (rho > 8.f * kEps * fmaxf(scale, __int_as_float(ws.tmax))) {
-            skip = 0;
-            const float z = ws.zs[p];
-            ws.zh[p] = rho * z * z;
-            if (p > lo) {
-              const float cur = ws.ds[p], prev = ws.ds[p - 1];
-              const float gap = 4.f * kEps * fmaxf(fabsf(cur), fabsf(prev)) + 1e-10f * scale;
-              if (cur < prev + gap) ws.fix[blk] = 1;
-            }
-          }
-        }
-        if (p == lo) {
-          ws.rho[blk] = rho;
-          ws.skip[blk] = skip;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid * bs < n && ws.fix[tid]) {  // rare: push equal poles a few ulps apart
-      const int blo = tid * bs, bhi = (blo + bs < n) ? blo + bs : n;
-      const float scale = fmaxf(__int_as_float(ws.bmax[tid]), ws.rho[tid]);
-      float prev = ws.ds[blo];
-      for (int j = blo + 1; j < bhi; ++j) {
-        float cur = ws.ds[j];
-        const float gap = 4.f * kEps * fmaxf(fabsf(cur), fabsf(prev)) + 1e-10f * scale;
-        if (cur < prev + gap) cur = prev + gap;
-        ws.ds[j] = cur;
-        prev = cur;
-      }
-      ws.fix[tid] = 0;
-    }
-    __syncthreads();
+    merge_order(Q, n, ws, map, h);      // ---- L1: z, merged order, max |d| per merge  (thread g = original column)
+    map.order();
+    merge_coupling(n, ws, map, h);      // ---- L2: coupling test, rz = rho z^2, poles that need separating  (p = sorted position)
+    map.order();
+    merge_separate(n, ws, map, bs);
+    map.order();
     UGLAD_STAMP(ws, 3 + 5 * lvl);
     if (last != nullptr && bs >= n) {  // (uniform) the last merge is carried out by other launches
       if (tid < n) {
@@ -663,98 +704,38 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
     // ---- L3: secular roots, four lanes per root, the lane's poles in registers.  (Measured: ONE lane per root at the small
     // merges -- a quarter of the issue slots -- is slower, 15 k instead of 9 k cycles per level: the solve is a dependent
     // chain, and what counts is its length per lane, not the number of lanes.)
+    constexpr int LR = (kThreads / DP >= 4) ? 4 : 2;
     {
-      auto roots = [&](auto lpr_c, auto np_c) {
+      auto roots = [&](auto lpr_c, auto np_c, int first) {  // roots first .. first + kThreads / L - 1
         constexpr int L = decltype(lpr_c)::value, NPv = decltype(np_c)::value;
-        const int pr_ = tid / L, sb = tid % L;
-        if (pr_ < n) {
-          const int blk = pr_ / bs, lo_ = blk * bs;
-          const int hi_ = (lo_ + bs < n) ? lo_ + bs : n;
-          const bool on = (lo_ + h < n) && (ws.skip[blk] == 0);
-          int K = pr_ - lo_;
+        const int p = first + map.root(L), sub = map.sub(L);
+        if (p < n) {
+          const MergeSpan s = merge_span(ws, map, p, h, n);
+          int K = p - s.lo;
           float mu = 0.f;
           int evals = 0;
-          if (on) evals = secular_root_reg<L, NPv>(ws.ds + lo_, ws.zh + lo_, ws.rho[blk], hi_ - lo_, pr_ - lo_, sb, K, mu);
-#ifdef UGLAD_STAMPS
-          if (sb == 0 && lvl < 14) {
-            atomicMax(reinterpret_cast<int*>(&ws.stamp[80 + lvl]), evals);
-            atomicAdd(reinterpret_cast<int*>(&ws.stamp[80 + lvl]) + 1, evals);
-          }
-#else
-          (void)evals;
-#endif
-          if (sb == 0) {
-            const float dK = ws.ds[lo_ + K];
-            ws.dk[pr_] = dK;
-            ws.mu[pr_] = mu;
-            ws.lam[pr_] = dK + mu;
-          }
+          if (s.act) evals = secular_root_reg<L, NPv>(ws.ds + s.lo, ws.zh + s.lo, ws.rho[map.slot(p, bs)], s.hi - s.lo, p - s.lo, sub, K, mu);
+          if (sub == 0) store_root(ws, p, s.lo, K, mu, evals, lvl);
         }
       };
       using std::integral_constant;
-      constexpr int LR = (kThreads / DP >= 4) ? 4 : 2;
       if (bs <= 64) {
-        roots(integral_constant<int, LR>(), integral_constant<int, 64 / LR>());
+        roots(integral_constant<int, LR>(), integral_constant<int, 64 / LR>(), 0);
       } else if (bs == 128) {
-        roots(integral_constant<int, LR>(), integral_constant<int, 128 / LR>());  // (64 poles per lane at LR = 2: 256-register kernels only)
+        roots(integral_constant<int, LR>(), integral_constant<int, 128 / LR>(), 0);  // (64 poles per lane at LR = 2: 256-register kernels only)
       } else {
         // bs = 256 (D > 128): 256 poles are too many for the registers of two or four lanes -- EIGHT lanes per root, 32 poles each,
         // 64 roots per pass (two lanes per root with the poles read from LDS took 180 k cycles here)
-        for (int pass = 0; 64 * pass < n; ++pass) {
-          const int pr_ = 64 * pass + tid / 8, sb = tid % 8;
-          if (pr_ < n) {
-            const int blk = pr_ / bs, lo_ = blk * bs;
-            const int hi_ = (lo_ + bs < n) ? lo_ + bs : n;
-            int K = pr_ - lo_;
-            float mu = 0.f;
-            if ((lo_ + h < n) && (ws.skip[blk] == 0))
-              (void)secular_root_reg<8, 32>(ws.ds + lo_, ws.zh + lo_, ws.rho[blk], hi_ - lo_, pr_ - lo_, sb, K, mu);
-            if (sb == 0) {
-              const float dK = ws.ds[lo_ + K];
-              ws.dk[pr_] = dK;
-              ws.mu[pr_] = mu;
-              ws.lam[pr_] = dK + mu;
-            }
-          }
-        }
+        for (int pass = 0; 64 * pass < n; ++pass) roots(integral_constant<int, 8>(), integral_constant<int, 32>(), 64 * pass);
       }
     }
-    __syncthreads();
+    map.order();
     UGLAD_STAMP(ws, 4 + 5 * lvl);
-    {  // ---- L4: Gu-Eisenstat zhat (pole j = p), stored with its pole in the ORIGINAL column order for the GEMM's B operand
-      constexpr int LPR = (kThreads / DP >= 4) ? 4 : 2;
-      const int p = tid / LPR, sub = tid % LPR;
-      int lo = 0, hi = 0;
-      bool act = false;
-      if (p < n) {
-        const int blk = p / bs;
-        lo = blk * bs;
-        hi = (lo + bs < n) ? lo + bs : n;
-        act = (lo + h < n) && (ws.skip[blk] == 0);
-      }
-      float prod = 1.f;
-      if (act) {
-        const float dj = ws.ds[p];
-#pragma unroll 4
-        for (int i = lo + sub; i < hi; i += LPR) {
-          const float num = (ws.dk[i] - dj) + ws.mu[i];
-          const float den = (i == p) ? 1.f : ws.ds[i] - dj;
-          prod *= num * fast_rcp(den);
-        }
-      }
-      prod = group_prod<LPR>(prod);
-      if (sub == 0 && p < n) {
-        ws.act[p] = act ? 1 : 0;
-        ws.nrm2[p] = 0.f;
-        if (act) {
-          const float zhat = sqrtf(fmaxf(prod, 0.f));
-          const int g = ws.perm[p];
-          ws.invo[g] = (ws.zs[p] < 0.f) ? -zhat : zhat;
-          ws.dso[g] = ws.ds[p];
-        }
-      }
+    {  // ---- L4: Gu-Eisenstat zhat, LR lanes per pole (the merge of the pole is looked up again: nothing lives across the solve)
+      const int p = map.root(LR), sub = map.sub(LR);
+      merge_zhat<LR>(n, ws, map, p, sub, merge_span(ws, map, p, h, n));
     }
-    __syncthreads();
+    map.order();
     UGLAD_STAMP(ws, 5 + 5 * lvl);
     {  // ---- L7: Q <- (Q W') diag(1/||W'_i||) on the diagonal blocks of size tb, W' generated per lane
       const int tb = (bs > 32) ? bs : 32;
@@ -800,9 +781,9 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             const int k = k0 + 2 * u + kh;
-            const float val = acti ? iv[u] * fast_rcp((dv[u] - dki) - mui) : ((k == permi) ? 1.f : 0.f);
+            const float val = merge_entry(acti, iv[u], dv[u], dki, mui, k, permi);
             s2 = fmaf(val, val, s2);
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[u], val, acc[0], 0, 0, 0);
+            acc[0] =__builtin_amdgcn_mfma_f32_32x32x2f32(av0[u], val, acc[0], 0, 0, 0);
             acc[kTPW - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[u], val, acc[kTPW - 1], 0, 0, 0);
           }
 #pragma unroll
@@ -861,9 +842,8 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
 #pragma unroll
               for (int u = 0; u < 8; ++u) {
                 const int k = k0 + 2 * u + kh;
-                float val = acti ? iv[u] * fast_rcp((dv[u] - dki) - mui) : ((k == permi) ? 1.f : 0.f);
-                if (bs < 32 && (unsigned)(k - blo) >= (unsigned)bs) val = 0.f;
-                s2 = fmaf(val, val, s2);
+                const float val = merge_entry(acti, iv[u], dv[u], dki, mui, k, permi, bs < 32, blo, bs);
+                s2 =fmaf(val, val, s2);
                 acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], val, acc[s], 0, 0, 0);
               }
 #pragma unroll
@@ -893,10 +873,9 @@ __device__ __forceinline__ void dc_tridiagonal_lean(float* __restrict__ Q, int n
         }
       }
       }  // !paired
-      if (tid < n) ws.d[tid] = ws.lam[tid];
-      if (tid < DP / 2 + 1) ws.bmax[tid] = 0;
+      merge_finish(n, ws, map);
     }
-    __syncthreads();
+    map.order();
     UGLAD_STAMP(ws, 6 + 5 * lvl);
   }
 }

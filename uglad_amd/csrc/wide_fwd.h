@@ -77,22 +77,16 @@ __global__ __launch_bounds__(kWThreads) void wide_merge_kernel(const float* __re
   if (tid < n && !skip) {
     const float dj = s_ds[tid];
     float prod = 1.f;
-    for (int i = 0; i < n; ++i) {
-      const float num = (s_dk[i] - dj) + s_mu[i];
-      const float den = (i == tid) ? 1.f : s_ds[i] - dj;
-      prod *= num * fast_rcp(den);
-    }
-    const float zhat = sqrtf(fmaxf(prod, 0.f));
+    for (int i = 0; i < n; ++i) prod *= zhat_factor(s_dk, s_mu, s_ds, i, tid, dj);  // (all poles in one lane, in this order)
     const int g = s_perm[tid];
-    s_invo[g] = (zs < 0.f) ? -zhat : zhat;
+    s_invo[g] = signed_zhat(prod, zs);
     s_dso[g] = dj;
   }
   __syncthreads();
   // B(k, j): column j = sorted position of the root, k = original column
   auto wgen = [&](int k, int j) -> float {
     if (j >= n || k >= n) return (k == j) ? 1.f : 0.f;                      // padding: identity
-    if (skip) return (k == s_perm[j]) ? 1.f : 0.f;                          // uncoupled halves: the merge only sorts
-    return s_invo[k] * fast_rcp((s_dso[k] - s_dk[j]) - s_mu[j]);
+    return merge_entry(!skip, s_invo[k], s_dso[k], s_dk[j], s_mu[j], k, s_perm[j]);  // (uncoupled halves: the merge only sorts)
   };
   {  // norms of this tile's 64 columns: thread (c = tid % 64, part = tid / 64) sums a quarter of the k range
     const int c = tid & 63, part = tid >> 6, j = j0 + c;
