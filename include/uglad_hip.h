@@ -330,6 +330,37 @@ int uglad_association(const double* table, int K, int N, int D, const int* col_f
                       const int* feat_width, const int* tile_first, int W, double eval_offset, float* A_out, double* A64_out,
                       double* min_eig_out, float* workspace, uglad_stream_t stream);
 
+/* The rank-based correlation matrix of K tables, the front-end of the nonparanormal (Gaussian copula) model, and the repair on it
+ * (csrc/rank_wide.h).  X is a DEVICE pointer to (K, N, D) row-major FP64 tables.  Every column is ranked by r2_a = 2 #{b : x_b < x_a} +
+ * #{b : x_b = x_a} + 1, twice scipy's rankdata(method="average"), an int32; +-Inf rank like any value.  method:
+ *   UGLAD_RANK_SPEARMAN  rho_ij = g_ij / (sqrt(g_ii) sqrt(g_jj)), g = sum_a c_ai c_aj, c = r2 - (N + 1), exact integers; transform = 1
+ *                        maps it through 2 sin(pi rho / 6)
+ *   UGLAD_RANK_KENDALL   tau-b: tau_ij = G_ij / (sqrt(G_ii) sqrt(G_jj)), G = s^T s over the N (N - 1) / 2 row pairs a < b with
+ *                        s = sign(x_a - x_b): G_ij = concordant - discordant pairs, G_ii = pairs not tied in column i, exact integers formed
+ *                        on v_mfma_i32_16x16x64_i8; transform = 1 maps it through sin(pi tau / 2)
+ *   UGLAD_RANK_SCORES    Pearson's r of the normal scores z = Phi^-1(r2 / (2 (N + 1))), g = their centred sums of products (not divided
+ *                        by N); transform is ignored
+ * A_out (K, D, D) fp32 receives the matrix, exactly symmetric, its diagonal exactly 1 before the repair; A64_out (K, D, D) fp64, optional,
+ * the same before the one rounding and ALWAYS unrepaired; gram_out (K, D, D) fp64, optional, g or G above, exactly symmetric; info_out
+ * (K, D) int32, optional: bit 0 set for a column that holds a NaN, bit 1 for a constant column.  Either flag gives NaN in that feature's
+ * row and column of the matrix and nowhere else (without repair); a NaN column also in gram_out.  min_eig_out NULL: no repair.
+ * Otherwise (K doubles), as uglad_association -- the transforms do not preserve positive semi-definiteness --: a table whose smallest
+ * eigenvalue is <= 1e-6 gets A_out += (eval_offset - min eig) I and min_eig_out[k] = that eigenvalue, by 48 bisection steps over
+ * [-||A||_inf, 1e-6]; a table that passes at 1e-6 gets +infinity.  Many workgroups per table, no host readback, no allocation; every
+ * result is bit-reproducible and does not depend on K, on the table's place in the batch or, for Kendall, on
+ * uglad_rank_correlation_pair_chunks(K, N, D), the number of chunks the pairs of a tile of G are dealt over (their int32 partial tiles
+ * are combined by integer atomics).  workspace: uglad_rank_correlation_workspace_floats(K, N, D, method) floats, 8-byte aligned
+ * (UGLAD_E_NULL otherwise).  2 <= D <= uglad_max_dim(), 2 <= N <= 65536 (where G_ii reaches 2^31), K <= 65535 (UGLAD_E_DIM otherwise);
+ * an unknown method or a transform that is not 0 / 1 gives UGLAD_E_MODE; the workspace size is negative on bad arguments (UGLAD_E_DIM,
+ * UGLAD_E_MODE) or beyond 2^31 - 1 floats (UGLAD_E_DIM). */
+#define UGLAD_RANK_SPEARMAN 0
+#define UGLAD_RANK_KENDALL 1
+#define UGLAD_RANK_SCORES 2
+int uglad_rank_correlation_workspace_floats(int K, int N, int D, int method);
+int uglad_rank_correlation_pair_chunks(int K, int N, int D);
+int uglad_rank_correlation(const double* X, int K, int N, int D, int method, int transform, double eval_offset, float* A_out,
+                           double* A64_out, double* gram_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
+
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
  * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k; workspace receives d, e, tau
  * (3 x 32*ceil(D/32) floats per matrix).  uglad_cell_fwd / uglad_symeig / uglad_init_theta / uglad_loss_fwd launch this

@@ -67,6 +67,10 @@ _SIGS = {
     "uglad_association_workspace_floats": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_association": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_double,
                            _c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_rank_correlation_workspace_floats": ([ctypes.c_int] * 4, ctypes.c_int),
+    "uglad_rank_correlation_pair_chunks": ([ctypes.c_int] * 3, ctypes.c_int),
+    "uglad_rank_correlation": ([ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_double, _c_float_p] + [ctypes.c_void_p] * 4
+                               + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
@@ -114,6 +118,18 @@ class GraphWide(NamedTuple):
     degree: torch.Tensor               # (K, D) int32
     triangles2: Optional[torch.Tensor]  # (K, D) int32: twice the triangles at every node
     stats: Optional[torch.Tensor]      # (K, 6) float64: num_nodes, num_edges, avg_degree, density, avg_clustering, transitivity
+
+
+RANK_METHODS = {"spearman": 0, "kendall": 1, "scores": 2}  # UGLAD_RANK_*
+
+
+class RankCorrelation(NamedTuple):
+    """What uglad_rank_correlation leaves on the device for K tables (include/uglad_hip.h)."""
+    A: torch.Tensor                   # (K, D, D) float32, repaired when asked
+    min_eig: Optional[torch.Tensor]   # (K,) float64, +inf for a table that needed no repair
+    A64: Optional[torch.Tensor]       # (K, D, D) float64, unrepaired
+    gram: Optional[torch.Tensor]      # (K, D, D) float64
+    info: torch.Tensor                # (K, D) int32: bit 0 NaN, bit 1 constant
 
 
 class HipLib:
@@ -395,6 +411,37 @@ class HipLib:
         self._call("uglad_association", self._vp(table64), K, N, D, *[self._vp(a) for a in ints], W, float(eval_offset), self._p(A),
                    self._vp(A64), self._vp(mn), self._p(wsp))
         return A, mn, A64
+
+    def rank_correlation(self, X64, method, transform: bool = True, eval_offset: float = 0.1, repair: bool = True, want_f64: bool = False,
+                         want_gram: bool = False) -> "RankCorrelation":
+        """(K,N,D) FLOAT64 tables on the device -> RankCorrelation (uglad_rank_correlation): the rank-based correlation matrix of the
+        nonparanormal model by `method` ("spearman", "kendall", "scores" or its UGLAD_RANK_* number): A (K,D,D) fp32 -- with `transform`
+        2 sin(pi rho / 6) or sin(pi tau / 2) --, repaired like a covariance when `repair`; min_eig (K,) fp64 (the smallest eigenvalue
+        before the repair, +inf for a table that needed none; None without `repair`); A64 (K,D,D) fp64 unrepaired (None without
+        `want_f64`); gram (K,D,D) fp64, the integer Gram matrix the coefficients are ratios of (None without `want_gram`); info (K,D)
+        int32, bit 0: the column holds a NaN, bit 1: it is constant -- NaN in that feature's row and column of A."""
+        self._require_f64(X64, 3, "rank_correlation takes a contiguous (K, N, D) float64 tensor")
+        if method not in RANK_METHODS and method not in RANK_METHODS.values():
+            raise UgladError(f"rank_correlation: method {method!r} is none of {sorted(RANK_METHODS)}")
+        m = RANK_METHODS.get(method, method)
+        K, N, D = X64.shape
+        dev = X64.device
+        wsp = self._wide_workspace("uglad_rank_correlation", dev, K, N, D, m)
+        A = torch.empty(K, D, D, dtype=torch.float32, device=dev)
+        A64 = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_f64 else None
+        gram = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_gram else None
+        info = torch.empty(K, D, dtype=torch.int32, device=dev)
+        mn = torch.empty(K, dtype=torch.float64, device=dev) if repair else None
+        self._call("uglad_rank_correlation", self._vp(X64), K, N, D, int(m), int(bool(transform)), float(eval_offset), self._p(A),
+                   self._vp(A64), self._vp(gram), self._vp(info), self._vp(mn), self._p(wsp))
+        return RankCorrelation(A, mn, A64, gram, info)
+
+    def rank_pair_chunks(self, K: int, N: int, D: int) -> int:
+        """The number of chunks a Kendall call of this shape deals the row pairs of a tile over (uglad_rank_correlation_pair_chunks)."""
+        n = int(self._dll.uglad_rank_correlation_pair_chunks(int(K), int(N), int(D)))
+        if n < 0:
+            self._check("uglad_rank_correlation_pair_chunks", n)
+        return n
 
     def conditional_mean(self, precision, mean, observed, values, clip01: bool = False):
         """uglad_conditional_mean: (K,D,D), (K,D), (K,D) mask, (K,D) -> full_mean (K,D), cond_cov (K,D,D), log_pdf (K)."""

@@ -100,6 +100,7 @@ __global__ __launch_bounds__(kWThreads) void covw_stats_kernel(const double* __r
 // grid (DP / 64, DP / 64, K); tiles below the diagonal return.  Ragged N and D are zero-filled AFTER centring.  The statistics are
 // covw_stats_kernel's, in vec3 of v's slab (normalize = 0 wrote mn = 0, scale = 1: the loader's (x - 0) * 1 - mu is x - mu to the bit).
 // Sink (the caller's): the types View (vec3(t) and DP as CholwView has them) and Out; every thread builds its own as Sink{v, out, D};
+//   kSums                       false: cov = S(i, j), the sum / N; true: the centred sum itself (rank_wide.h: exact integers stay exact)
 //   put(t, i, j, cov, inside)   per element of the upper triangle of the padded matrix, i <= j < DP; cov = S(i, j) where inside (j < D)
 //   finish(t, I, J)             behind the tile's last put, called by the whole workgroup
 template <class Sink>
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(kWThreads) void covw_gram_kernel(const double* __re
   t64_for_each_fragment([&](int a, int c, int r, int row, int cl) {
     const int i = I * kT64 + row, j = J * kT64 + cl;
     if (i > j) return;  // (the diagonal tile: its lower half is the mirror of its upper half)
-    sink.put(t, i, j, acc[a][c][r] / (double)N, j < D);  // (i <= j)
+    sink.put(t, i, j, Sink::kSums ? acc[a][c][r] : acc[a][c][r] / (double)N, j < D);  // (i <= j)
   });
   sink.finish(t, I, J);
 }
@@ -140,6 +141,7 @@ __device__ __forceinline__ void covw_store(T* M, int ld, int i, int j, T val, bo
 struct CovwSink {
   using View = CholwView;
   using Out = float;
+  static constexpr bool kSums = false;
   CholwView v;
   float* S_out;
   int D;

@@ -141,6 +141,7 @@ __global__ __launch_bounds__(kWThreads) void eigw_prepare_kernel(const double* _
 struct EigwGramSink {
   using View = EigwView;
   using Out = double;
+  static constexpr bool kSums = false;
   EigwView v;
   double* cov_out;
   int D;

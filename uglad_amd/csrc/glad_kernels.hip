@@ -43,6 +43,7 @@ namespace uglad {
 #include "chol_wide.h"
 #include "cov_wide.h"
 #include "assoc_wide.h"
+#include "rank_wide.h"
 #include "after_wide.h"
 #include "score_wide.h"
 #include "sort_wide.h"

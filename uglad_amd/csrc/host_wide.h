@@ -160,6 +160,62 @@ int uglad_association(const double* table, int K, int N, int D, const int* col_f
   return launch_status();
 }
 
+// uglad_rank_correlation's arguments: the dimensions first, then the method
+static int rank_arguments(int K, int N, int D, int method) {
+  if (K < 1 || K > 65535 || D < 2 || D > UGLAD_MAX_DIM || N < 2 || N > kRankMaxN) return UGLAD_E_DIM;
+  return method == kRankSpearman || method == kRankKendall || method == kRankScores ? 0 : UGLAD_E_MODE;
+}
+static_assert(UGLAD_RANK_SPEARMAN == kRankSpearman && UGLAD_RANK_KENDALL == kRankKendall && UGLAD_RANK_SCORES == kRankScores,
+              "the header's constants are the kernels'");
+
+int uglad_rank_correlation_workspace_floats(int K, int N, int D, int method) {
+  const int rc = rank_arguments(K, N, D, method);
+  if (rc != 0) return rc;
+  return wide_workspace_floats(K, D, 2, [N, method](int D) { return rank_table_floats(N, D, method); });
+}
+
+// Kendall: enough chunks of pairs for about eight workgroups per compute unit, but none below 32 steps of 64 pairs (a chunk ends in T x T
+// atomics) and none without a shift of its own
+int uglad_rank_correlation_pair_chunks(int K, int N, int D) {
+  if (rank_arguments(K, N, D, kRankKendall) != 0) return UGLAD_E_DIM;
+  const int T = rank_tile(D), nt = rank_padded_tiles(D) / T;
+  const long long groups = (long long)K * (nt * (nt + 1) / 2);
+  const long long steps = (long long)N * (N - 1) / 2 / kRankStep + (N - 1) / 2 + 1;  // (the tail of a shift is half a step on average)
+  long long chunks = (2048 + groups - 1) / groups;
+  if (chunks > steps / 32) chunks = steps / 32;
+  if (chunks > N - 1) chunks = N - 1;
+  return chunks < 1 ? 1 : (int)chunks;
+}
+
+int uglad_rank_correlation(const double* X, int K, int N, int D, int method, int transform, double eval_offset, float* A_out,
+                           double* A64_out, double* gram_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream) {
+  if (!X || !A_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  const int rc = rank_arguments(K, N, D, method);
+  if (rc != 0) return rc;
+  if (uglad_rank_correlation_workspace_floats(K, N, D, method) < 0) return UGLAD_E_DIM;
+  if (transform != 0 && transform != 1) return UGLAD_E_MODE;
+  hipStream_t st = (hipStream_t)stream;
+  const RankView v = rank_view(workspace, K, N, D);
+  const int DP = v.c.DP, nt64 = DP / kT64;
+  const dim3 wg(kWThreads);
+  hipLaunchKernelGGL(rank_kernel, dim3((N + kWThreads - 1) / kWThreads, D, K), wg, 0, st, X, N, D, method, v, info_out);
+  if (method == kRankKendall) {
+    const int T = rank_tile(D), nt = v.DT / T;
+    const dim3 grid(nt * (nt + 1) / 2, uglad_rank_correlation_pair_chunks(K, N, D), K);
+    zero_floats(reinterpret_cast<float*>(v.gram32(0, D)), (size_t)K * v.DT * v.DT, st);  // (int32 zeros are float zeros)
+    if (T == kRankTileWide) hipLaunchKernelGGL(rank_kendall_kernel<kRankTileWide / 32>, grid, wg, 0, st, N, D, v);
+    else hipLaunchKernelGGL(rank_kendall_kernel<kRankTileNarrow / 32>, grid, wg, 0, st, N, D, v);
+  } else {  // the centred sums of the table of c or z, as a covariance's
+    hipLaunchKernelGGL(covw_stats_kernel, dim3(nt64, K), wg, 0, st, (const double*)v.table(), N, D, 0, v.c);
+    hipLaunchKernelGGL(covw_gram_kernel<RankGramSink>, dim3(nt64, nt64, K), wg, 0, st, (const double*)v.table(), N, D, v.c, (double*)nullptr);
+  }
+  hipLaunchKernelGGL(rank_finish_kernel, dim3(DP * DP / kWThreads, K), wg, 0, st, D, method, transform, v, A_out, A64_out, gram_out);
+  if (!min_eig_out) return launch_status();  // no repair
+  hipLaunchKernelGGL(assoc_rowsum_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, v.c);
+  launch_cholw_bisection<AssocBracket>(st, K, D, eval_offset, v.c, A_out, min_eig_out);
+  return launch_status();
+}
+
 int uglad_conditional_mean_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, afterw_problem_floats); }
 
 int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,

@@ -212,6 +212,36 @@ def mixed_association(df, dtype, repair: bool = True, eval_offset: float = 0.1):
     return A[0], (None if mn is None else float(mn[0]))
 
 
+def _rank_tables(X):
+    """(tables (K, N, D) float64 contiguous, single, names): an (N, D) array or DataFrame, or a list / (K, N, D) array of tables."""
+    names = [str(c) for c in X.columns] if hasattr(X, "columns") else None
+    single = hasattr(X, "columns") or (not isinstance(X, (list, tuple)) and np.ndim(X) == 2)
+    tables = np.array(X, dtype=np.float64, order="C")  # (a copy of its own: the caller's array may be read-only)
+    tables = tables[None] if single else tables
+    if tables.ndim != 3:
+        raise ValueError("rank_correlation takes an (N, D) table, or a list / (K, N, D) array of tables of one shape")
+    if np.isnan(tables).any():
+        raise ValueError("rank_correlation: the table holds NaN; impute or drop those rows first")
+    return tables, single, names
+
+
+def rank_correlation(X, method: str = "kendall", transform: bool = True, repair: bool = True, eval_offset: float = 0.1):
+    """The rank-based correlation matrix of the nonparanormal (Gaussian copula) model, on the device (uglad_rank_correlation,
+    csrc/rank_wide.h; additive, what R's huge.npn offers): `method` "spearman" (with `transform` 2 sin(pi rho / 6)), "kendall" (tau-b,
+    sin(pi tau / 2): the SKEPTIC estimator) or "scores" (the correlation of Phi^-1(rank / (N + 1))).  X is an (N, D) array or DataFrame,
+    or a list / (K, N, D) array of tables of one shape.  Returns (A, min_eig) like mixed_association: A the (D, D) -- or (K, D, D) -- fp32
+    matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset - min eig) I), and min_eig the
+    smallest eigenvalue before the repair as a float -- or a (K,) float64 array -- (+inf where none was needed; None without `repair`).
+    A constant column gives NaN in its row and column; a NaN raises ValueError."""
+    tables, single, _ = _rank_tables(X)
+    out = _lib.get_lib().rank_correlation(torch.from_numpy(tables).to(_lib.device()), method, transform=transform,
+                                          eval_offset=eval_offset, repair=repair)
+    mn = None if out.min_eig is None else out.min_eig.cpu().numpy()
+    if single:
+        return out.A[0], (None if mn is None else float(mn[0]))
+    return out.A, mn
+
+
 def _print_every(EPOCHS: int) -> int:
     return max(1, int(EPOCHS / 10))
 
@@ -715,6 +745,48 @@ class uGLAD_GL(object):
             self.model_glad = model_glad
         self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
         self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit_mixed", None)
+        if verbose:
+            print(f"Total runtime: {time() - start} secs\n")
+        return compare_theta
+
+    def fit_copula(self, X, method="kendall", true_theta=None, eval_offset=0.1, epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True,
+                   sqrt_mode=None):
+        """`fit` under the nonparanormal (Gaussian copula) model (additive; the reference has no such option): for a table whose columns
+        are not Gaussian after any normalisation -- counts, concentrations, skewed and heavy-tailed measurements -- the covariance is
+        replaced by a rank-based correlation matrix, `method` "kendall", "spearman" or "scores" (rank_correlation), formed and repaired
+        on the device (uglad_rank_correlation), and direct-mode training runs on that matrix.  X is an (N, D) array or DataFrame.  Sets
+        covariance_ (the UNREPAIRED matrix, float64), precision_, location_ (the column means), node_names_ (a DataFrame's columns),
+        model_glad, cond_max_ and copula_min_eig_; predict(S=...), recovered_graph() and save / load work afterwards.  Direct mode
+        only: CV, missing and multitask modes are out of scope."""
+        start = time()
+        if verbose:
+            print("Running uGLAD on a rank correlation matrix")
+        tables, single, names = _rank_tables(X)
+        if not single:
+            raise ValueError("fit_copula takes one (N, D) table")
+        D = tables.shape[2]
+        names = names if names is not None else [f"node_{i}" for i in range(D)]
+        out = _lib.get_lib().rank_correlation(torch.from_numpy(tables).to(_lib.device()), method, transform=True, eval_offset=eval_offset,
+                                              repair=True, want_f64=True)
+        constant = np.nonzero(out.info[0].cpu().numpy() & 2)[0]
+        if len(constant):
+            raise ValueError(f"fit_copula: constant columns have no rank correlation: {[names[i] for i in constant]}")
+        true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
+        with glad.regime_monitor() as regime:
+            pred_theta, compare_theta, model_glad = run_uGLAD_direct(None, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs,
+                                                                     lr=lr, INIT_DIAG=INIT_DIAG, L=L, VERBOSE=verbose,
+                                                                     sqrt_mode=sqrt_mode, Sb=out.A)
+        self.covariance_ = out.A64[0].cpu().numpy()
+        self.copula_min_eig_ = float(out.min_eig[0])
+        self.location_ = tables[0].mean(axis=0)
+        self.data_min_ = self.data_range_ = None  # (rows of a copula fit are not scored)
+        self.node_names_ = names
+        if pred_theta is not None:
+            self.precision_ = pred_theta[0].detach().cpu().numpy()
+        if model_glad is not None:
+            self.model_glad = model_glad
+        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+        self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit_copula", None)
         if verbose:
             print(f"Total runtime: {time() - start} secs\n")
         return compare_theta

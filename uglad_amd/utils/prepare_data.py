@@ -21,6 +21,8 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
+from .. import _lib
+
 __all__ = [
     "generate_random_graph",
     "simulate_gaussian_samples",
@@ -541,6 +543,72 @@ def pairwise_cov_matrix(df, dtype):
 
     table, maps = encode_mixed_table(df, dtype)
     return pd.DataFrame(association_from_codes(table, maps.kinds, maps.cards), index=maps.names, columns=maps.names)
+
+
+# --------------------------------------------------------------------------- rank correlations (the nonparanormal front-end)
+# The host formulation of uglad_rank_correlation (csrc/rank_wide.h; additive, the reference has no such option): vectorised fp64 numpy.  The
+# tests' oracle beyond the goldens, and the probe's baseline.
+RANK_METHODS = tuple(_lib.RANK_METHODS)  # "spearman", "kendall", "scores": the names of UGLAD_RANK_* in their order, stated in _lib
+RANK_MAX_ROWS = 65536  # include/uglad_hip.h: where a diagonal entry of Kendall's Gram matrix reaches 2^31
+
+
+def doubled_midranks(X) -> np.ndarray:
+    """r2[a, i] = 2 #{b : x_bi < x_ai} + #{b : x_bi = x_ai} + 1 per column of an (N, D) table, int64: twice
+    scipy.stats.rankdata(method="average").  A NaN is below and equal to nothing, and nothing is below or equal to it."""
+    X = np.asarray(X, dtype=np.float64)
+    r2 = np.empty(X.shape, dtype=np.int64)
+    for i in range(X.shape[1]):
+        x = X[:, i]
+        s = np.sort(x[~np.isnan(x)])
+        r2[:, i] = np.where(np.isnan(x), 1, np.searchsorted(s, x, "left") + np.searchsorted(s, x, "right") + 1)
+    return r2
+
+
+def rank_gram_host(X, method: str, chunk_pairs: int = 8192) -> np.ndarray:
+    """The (D, D) float64 Gram matrix the coefficient of `method` is a ratio of (include/uglad_hip.h): for "spearman" sum_a c_ai c_aj with
+    c = r2 - (N + 1); for "kendall" G = s^T s over the N (N - 1) / 2 row pairs a < b, s = sign(x_a - x_b), as float64 BLAS products of
+    the sign rows in chunks -- both exact integers below 2^53; for "scores" the centred sums of products of Phi^-1(r2 / (2 (N + 1)))."""
+    if method not in RANK_METHODS:
+        raise ValueError(f"method {method!r} is none of {RANK_METHODS}")
+    r2 = doubled_midranks(X)
+    N, D = r2.shape
+    if method == "spearman":
+        c = (r2 - (N + 1)).astype(np.float64)
+        return c.T @ c
+    if method == "scores":
+        z = torch.special.ndtri(torch.from_numpy(r2.astype(np.float64) / (2.0 * (N + 1)))).numpy()
+        z = z - z.mean(axis=0)
+        return z.T @ z
+    G = np.zeros((D, D))
+    rows, held = [], 0
+    for a in range(N - 1):
+        rows.append(np.sign(r2[a] - r2[a + 1:]).astype(np.float64))
+        held += N - 1 - a
+        if held >= chunk_pairs or a == N - 2:
+            S = np.concatenate(rows)
+            G += S.T @ S
+            rows, held = [], 0
+    return G
+
+
+def rank_correlation_host(X, method: str, transform: bool = True) -> np.ndarray:
+    """The rank-based correlation matrix of an (N, D) table as uglad_rank_correlation defines it, float64, unrepaired: Spearman's rho
+    (`transform`: 2 sin(pi rho / 6)), Kendall's tau-b (`transform`: sin(pi tau / 2)) or the correlation of the normal scores; exactly 1
+    on the diagonal, NaN in the row and column of a feature that holds a NaN or is constant."""
+    X = np.asarray(X, dtype=np.float64)
+    g = rank_gram_host(X, method)
+    root = np.sqrt(np.diag(g))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        A = g / (root[:, None] * root[None, :])
+    if transform and method == "spearman":
+        A = 2.0 * np.sin(np.pi * A / 6.0)
+    if transform and method == "kendall":
+        A = np.sin(np.pi * A / 2.0)
+    A[np.diag_indices_from(A)] = 1.0
+    bad = np.isnan(X).any(axis=0) | (X == X[:1]).all(axis=0)
+    A[bad, :] = np.nan
+    A[:, bad] = np.nan
+    return A
 
 
 # --------------------------------------------------------------------------- bench inputs
