@@ -362,7 +362,8 @@ int uglad_rank_correlation(const double* X, int K, int N, int D, int method, int
                            double* A64_out, double* gram_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
 
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
- * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k; workspace receives d, e, tau
+ * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k, the rows without one (D-2, D-1) are
+ * zero; workspace receives d, e, tau
  * (3 x 32*ceil(D/32) floats per matrix).  uglad_cell_fwd / uglad_symeig / uglad_init_theta / uglad_loss_fwd launch this
  * kernel themselves before their divide & conquer kernel. */
 int uglad_tridiagonalize(const float* A0, const float* A1, const float* lam, float* R, float* workspace, int M, int D,

@@ -131,6 +131,9 @@ __global__ __launch_bounds__(TH, NT <= 4 ? 8 : (TH > 512 ? 1 : 2)) void tridiag_
   float* R = Rbase + base;
   float* tri = tri_base + (size_t)blockIdx.x * 3 * DP;
   const float inv_lam = lam_ptr ? 1.0f / lam_ptr[blockIdx.x / gs] : 1.0f;  // gs matrices share one lambda (one group)
+  // rows n-2 and n-1 of R hold no reflector: zero, so that the kernel defines all of R (it is the output of uglad_tridiagonalize; the cell
+  // and the factorisations overwrite it).  Issued before the loads, nothing waits for it
+  for (int i = tid; i < (n < 2 ? n : 2) * n; i += TH) R[(size_t)(n < 2 ? 0 : n - 2) * n + i] = 0.0f;
 
   // ---- load: coalesced along the rows of A (32 lanes x 16 bytes per column), LB column slots per batch.  Every load of a batch is
   // unconditional -- an entry outside the matrix reads the matrix's own first element and is replaced by zero afterwards -- so the

@@ -66,6 +66,8 @@ __global__ __launch_bounds__(64) void tridiag_wave_kernel(const float* __restric
   float* R = Rbase + base;
   float* tri = tri_base + (size_t)blockIdx.x * 3 * DP;
   const float inv_lam = lam_ptr ? 1.0f / lam_ptr[blockIdx.x / gs] : 1.0f;
+  // rows n-2 and n-1 of R hold no reflector: zero, so that the kernel defines all of R (see tridiag.h)
+  for (int i = lane; i < (n < 2 ? n : 2) * n; i += 64) R[(size_t)(n < 2 ? 0 : n - 2) * n + i] = 0.0f;
 
   // ---- load: register r = entry (row hf RPL + r, column c); a wave reads whole rows (the matrix is symmetric)
   // LR rows per batch (at 16 the kernel passes 64 VGPRs, a wave per SIMD fewer), every load unconditional (an entry outside the matrix
