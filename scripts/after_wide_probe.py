@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the device conditional Gaussian beyond D = 256 (uglad_conditional_mean_wide, csrc/after_wide.h) against the host formulation it
-replaces (main._conditional_gaussian_host: np.linalg.inv and slogdet in fp64, one problem at a time), on the same problems.
+replaces (after._conditional_gaussian_host: np.linalg.inv and slogdet in fp64, one problem at a time), on the same problems.
 
     python scripts/after_wide_probe.py [--out profiles/after_wide_probe.txt] [--dims 288,1024,2048]
 
@@ -40,14 +40,14 @@ def main():
     ap.add_argument("--dims", default="288,1024,2048")
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
-    from uglad_amd import _lib, main as um
+    from uglad_amd import _lib, after, main as um
 
     if not torch.cuda.is_available():
         raise SystemExit("after_wide_probe.py measures on the GPU; none is visible")
     lib = _lib.get_lib()
     dev = _lib.device()
     lines = [f"# scripts/after_wide_probe.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}; median of {args.reps} after one warm-up",
-             "# host = main._conditional_gaussian_host (fp64 numpy, per problem); device = HIP events around conditional_mean_wide; e2e = "
+             "# host = after._conditional_gaussian_host (fp64 numpy, per problem); device = HIP events around conditional_mean_wide; e2e = "
              "main.conditional_gaussian_batch on host arrays",
              f"{'D':>5} {'K':>2} {'cov':>4} {'host ms':>10} {'device ms':>10} {'e2e ms':>9} {'host/e2e':>9} {'mean':>9} {'cov':>9} {'logp':>9}"]
     print("\n".join(lines), flush=True)
@@ -57,7 +57,7 @@ def main():
             host_ms = []
             for rep in range(args.reps + 1):
                 t0 = time.perf_counter()
-                h_full, h_cov, h_logp = um._conditional_gaussian_host(P, mu, mask, vals, False, dev)
+                h_full, h_cov, h_logp = after._conditional_gaussian_host(P, mu, mask, vals, False, dev)
                 torch.cuda.synchronize()
                 if rep:
                     host_ms.append((time.perf_counter() - t0) * 1e3)

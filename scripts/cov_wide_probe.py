@@ -6,9 +6,9 @@ under device_covariance=True (prepare_data.get_covariance: fp64 numpy, one non-s
 
 Tables: K x N x D.  N = D / 2: mixed Gaussian factors, singular, so both sides repair them and the device bisects; N = 2 D: uniform columns,
 well conditioned, so the device leaves after the one factorisation at the threshold while the host still runs its eigvals.  Columns:
-  host ms     wall clock of get_covariance + the upload of S (what main._covariance does without device_covariance), one run
+  host ms     wall clock of get_covariance + the upload of S (what inputs._covariance does without device_covariance), one run
   device ms   HIP events around the enqueue of covariance_wide on tables already on the device: median of the timed runs after a warm-up
-  e2e ms      wall clock of main._covariance under device_covariance(True): upload of the fp64 tables, kernels, synchronise (median)
+  e2e ms      wall clock of inputs._covariance under device_covariance(True): upload of the fp64 tables, kernels, synchronise (median)
 No threshold: the table reports, whichever side wins."""
 import argparse
 import os
@@ -41,14 +41,14 @@ def main():
     ap.add_argument("--dims", default="288,1024,2048")
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
-    from uglad_amd import _lib, main as um
+    from uglad_amd import _lib, inputs, main as um
     from uglad_amd.utils import prepare_data
 
     if not torch.cuda.is_available():
         raise SystemExit("cov_wide_probe.py measures on the GPU; none is visible")
     lib = _lib.get_lib()
     lines = [f"# scripts/cov_wide_probe.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}; reps {args.reps} after one warm-up",
-             "# host = prepare_data.get_covariance (fp64 numpy) + upload; device = HIP events around covariance_wide; e2e = main._covariance "
+             "# host = prepare_data.get_covariance (fp64 numpy) + upload; device = HIP events around covariance_wide; e2e = inputs._covariance "
              "under device_covariance(True)",
              f"{'D':>5} {'N':>5} {'K':>2} {'repaired':>8} {'host ms':>10} {'device ms':>10} {'e2e ms':>9} {'host/e2e':>9} {'rel-Frobenius':>14}"]
     print("\n".join(lines), flush=True)
@@ -57,7 +57,7 @@ def main():
             for K in (1, 4):
                 X = make_tables(K, N, D, seed=D + N + K)
                 t0 = time.perf_counter()
-                S_host = um._to_dev(prepare_data.get_covariance(X, offset=0.1))
+                S_host = inputs._to_dev(prepare_data.get_covariance(X, offset=0.1))
                 torch.cuda.synchronize()
                 host_ms = (time.perf_counter() - t0) * 1e3
                 Xd = torch.from_numpy(X).cuda()
@@ -70,7 +70,7 @@ def main():
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     with um.device_covariance(True):
-                        S_e2e = um._covariance(list(X), 0.1)
+                        S_e2e = inputs._covariance(list(X), 0.1)
                     torch.cuda.synchronize()
                     if rep:  # (the first run is the warm-up of both)
                         dev_ms.append(start.elapsed_time(stop))

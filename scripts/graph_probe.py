@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the recovered graph on the device (uglad_graph_wide, csrc/graph_wide.h) against the package's own host formulation of the same
-definitions (main._recovered_graph_host: float64, vectorised -- sort, compare, (A A) o A through BLAS), on the same partial correlations.
+definitions (after._recovered_graph_host: float64, vectorised -- sort, compare, (A A) o A through BLAS), on the same partial correlations.
 
     python scripts/graph_probe.py [--out profiles/graph_probe.txt] [--dims 288,1024,2048]
 
@@ -12,7 +12,7 @@ edges inside the communities only).  Columns:
   nx ms       networkx average_clustering + transitivity on problem 0's graph (what the reference's compute_graph_statistics calls), ONE run,
               the graph already built; not part of `host ms`
   device ms   HIP events around the enqueue of graph_wide on tensors already on the device
-  e2e ms      wall clock of main._recovered_graphs on those tensors: kernels, download of thresholds, counts, edge lists, degrees, triangles
+  e2e ms      wall clock of after._recovered_graphs on those tensors: kernels, download of thresholds, counts, edge lists, degrees, triangles
               and statistics, the result objects
   tri %       share of the device time that the triangle product, its row sums and the six statistics take: 1 - (device ms without
               statistics) / (device ms)
@@ -62,14 +62,14 @@ def main():
     args = ap.parse_args()
     import networkx as nx
 
-    from uglad_amd import _lib, main as um
+    from uglad_amd import _lib, after, main as um
 
     if not torch.cuda.is_available():
         raise SystemExit("graph_probe.py measures on the GPU; none is visible")
     lib = _lib.get_lib()
     lines = [f"# scripts/graph_probe.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}; median of {args.reps} after one warm-up (nx: one run)",
-             "# host = download + main._recovered_graph_host per problem; nx = networkx average_clustering + transitivity, problem 0; device = HIP "
-             "events around graph_wide; e2e = main._recovered_graphs on device tensors; tri % = share of the statistics kernels",
+             "# host = download + after._recovered_graph_host per problem; nx = networkx average_clustering + transitivity, problem 0; device = HIP "
+             "events around graph_wide; e2e = after._recovered_graphs on device tensors; tri % = share of the statistics kernels",
              f"{'pattern':>7} {'D':>5} {'K':>2} {'spars':>5} {'edges':>8} {'host ms':>9} {'nx ms':>9} {'device ms':>10} {'e2e ms':>8} {'host/e2e':>9} "
              f"{'tri %':>6} {'skipped':>8} {'same':>5}"]
     print("\n".join(lines), flush=True)
@@ -96,12 +96,12 @@ def main():
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
                         Rn = Rd.cpu().numpy()
-                        host = [um._recovered_graph_host(Rn[k], False, n_keep, None, True) for k in range(K)]
+                        host = [after._recovered_graph_host(Rn[k], False, n_keep, None, True) for k in range(K)]
                         t1 = time.perf_counter()
                         full = timed(lambda: lib.graph_wide(Rd, n_keep=n_keep, from_precision=False, want_stats=True))
                         lean = timed(lambda: lib.graph_wide(Rd, n_keep=n_keep, from_precision=False, want_stats=False))
                         t2 = time.perf_counter()
-                        got = um._recovered_graphs(Rd, False, n_keep, None, True)
+                        got = after._recovered_graphs(Rd, False, n_keep, None, True)
                         t3 = time.perf_counter()
                         if rep:  # (the first run is the warm-up of all)
                             host_ms.append((t1 - t0) * 1e3)

@@ -48,7 +48,6 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("metrics_wide_probe.py measures on the GPU; none is visible")
     lib = _lib.get_lib()
-    um.WIDE_METRICS_MIN_DIM = 0  # (measure the device on the whole range, whatever the shipped threshold)
     lines = [f"# scripts/metrics_wide_probe.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}; median of {args.reps} after one warm-up",
              "# host = download + utils.metrics.report_metrics_all per pair; device = HIP events around support_metrics_wide; e2e = "
              "main.device_report_metrics on device tensors",

@@ -168,7 +168,7 @@ def test_emulated_routing_needs_no_host(emul, monkeypatch):
     def no_host(*a, **k):
         raise AssertionError("the host formulation ran for a D the device covers")
 
-    monkeypatch.setattr(main, "_conditional_gaussian_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._conditional_gaussian_host", no_host)
     monkeypatch.setattr(emul, "max_eig_dim", 32)
     P, mu, mask, vals = problems(2, 70, seed=55)
     full, cov, logp = main.conditional_gaussian_batch(P, mu, mask.astype(np.float32), vals)
@@ -266,7 +266,7 @@ def test_emulated_matches_reference_goldens(emul, monkeypatch, name):
     def no_host(*a, **k):
         raise AssertionError("the host formulation ran for a D the device covers")
 
-    monkeypatch.setattr(main, "_conditional_gaussian_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._conditional_gaussian_host", no_host)
     _check_golden(name)
 
 
@@ -299,7 +299,7 @@ def test_gpu_main_routes_beyond_256_to_the_device(monkeypatch):
     def no_host(*a, **k):
         raise AssertionError("the host formulation ran for a D the device covers")
 
-    monkeypatch.setattr(main, "_conditional_gaussian_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._conditional_gaussian_host", no_host)
     P, mu, mask, vals = problems(2, 300, seed=63)
     full, cov, logp = uglad_amd.conditional_gaussian_batch(P, mu, mask.astype(np.float32), vals)
     assert full.is_cuda and full.dtype == cov.dtype == logp.dtype == torch.float32 and cov.shape == (2, 300, 300)

@@ -105,7 +105,7 @@ def test_ragged_tables_under_device_covariance(emul):
     """Missing mode hands K row-subsampled folds to the covariance front-end; with N % K != 0 they differ in length (and so
     may multitask tables).  The device path groups the tables by shape instead of stacking them into one array."""
     import uglad_amd
-    from uglad_amd import main
+    from uglad_amd import inputs, main
 
     rng = np.random.default_rng(5)
     X = rng.standard_normal((50, 6))  # 50 % 3 != 0: train folds of 33, 33, 34 rows
@@ -119,8 +119,8 @@ def test_ragged_tables_under_device_covariance(emul):
     assert relerr(out[1], out[0].astype(np.float64)) < 1e-4
     tabs = [rng.random((n, 5)) for n in (40, 31, 40)]
     with main.device_covariance(True):
-        S_dev = main._covariance(tabs, 0.1).numpy()
-    S_host = main._covariance(tabs, 0.1).numpy()
+        S_dev = inputs._covariance(tabs, 0.1).numpy()
+    S_host = inputs._covariance(tabs, 0.1).numpy()
     assert S_dev.shape == (3, 5, 5) and relerr(S_dev, S_host.astype(np.float64)) < TOL
 
 
@@ -128,7 +128,7 @@ def test_repair_decision_near_the_threshold_follows_fp64(emul):
     """The reference repairs where the fp64 minimum eigenvalue is <= 1e-6 (prepare_data.py:347-352).  An fp32 solver cannot
     resolve that threshold; tables whose covariance has its smallest eigenvalue within the guard band of it are re-decided on
     the host in fp64, so the device path and the host path take the same branch (the shift is an O(offset) step)."""
-    from uglad_amd import main
+    from uglad_amd import inputs, main
     from uglad_amd.utils import prepare_data as pd_
 
     rng = np.random.default_rng(9)
@@ -142,7 +142,7 @@ def test_repair_decision_near_the_threshold_follows_fp64(emul):
         tabs.append(U @ np.diag(s) @ Vt + B.mean(0))
     S_host = pd_.get_covariance(tabs, offset=0.1)
     with main.device_covariance(True):
-        S_dev = main._covariance(tabs, 0.1).numpy()
+        S_dev = inputs._covariance(tabs, 0.1).numpy()
     shifted_host = [np.linalg.eigvalsh(S).min() > 0.05 for S in S_host]
     shifted_dev = [np.linalg.eigvalsh(S.astype(np.float64)).min() > 0.05 for S in S_dev]
     assert shifted_host == shifted_dev == [True, True, False, False, False]

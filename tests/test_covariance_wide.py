@@ -129,7 +129,7 @@ def near_threshold_tables(N, D, seed=9):
 def test_emulated_repair_decision_near_the_threshold_needs_no_host(emul, monkeypatch):
     """Both sides of the reference's threshold of 1e-6 at D = 40, through main's routing (the library's eigensolver limit lowered so
     that D = 40 counts as wide): the device takes the reference's branch each time, and no fp64 eigvalsh runs on the host."""
-    from uglad_amd import main
+    from uglad_amd import inputs, main
     from uglad_amd.utils import prepare_data as pd_
 
     tabs = near_threshold_tables(64, 40)
@@ -142,7 +142,7 @@ def test_emulated_repair_decision_near_the_threshold_needs_no_host(emul, monkeyp
 
     monkeypatch.setattr(np.linalg, "eigvalsh", no_eigvalsh)
     with main.device_covariance(True):
-        S_dev = main._covariance(tabs, 0.1).numpy()
+        S_dev = inputs._covariance(tabs, 0.1).numpy()
     shifted_host = [bool(S_host[k][0, 0] - S_raw[k][0, 0] > 0.05) for k in range(5)]
     shifted_dev = [bool(S_dev[k][0, 0] - S_raw[k][0, 0] > 0.05) for k in range(5)]
     assert shifted_host == shifted_dev == [True, True, False, False, False]
@@ -249,19 +249,19 @@ def test_gpu_uniform_table_is_left_alone_and_nine_block_columns():
 
 @pytest.mark.gpu
 def test_gpu_main_routes_wide_ragged_tables_to_the_device(monkeypatch):
-    from uglad_amd import main
+    from uglad_amd import inputs, main
     from uglad_amd.utils import prepare_data as pd_
 
     rng = np.random.default_rng(43)
     tabs = [rng.random((n, 288)) for n in (40, 31, 40)]
-    S_host = main._covariance(tabs, 0.1).cpu().numpy()
+    S_host = inputs._covariance(tabs, 0.1).cpu().numpy()
 
     def no_host(*a, **k):
         raise AssertionError("the host covariance ran under device_covariance")
 
     monkeypatch.setattr(pd_, "get_covariance", no_host)
     with main.device_covariance(True):
-        S_dev = main._covariance(tabs, 0.1).cpu().numpy()
+        S_dev = inputs._covariance(tabs, 0.1).cpu().numpy()
     assert S_dev.shape == (3, 288, 288)
     for k in range(3):
         assert relerr(S_dev[k], S_host[k].astype(np.float64)) < TOL, (k, relerr(S_dev[k], S_host[k].astype(np.float64)))

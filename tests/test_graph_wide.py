@@ -339,7 +339,7 @@ def _check_golden(D):
 def test_emulated_matches_the_reference_golden(emul, monkeypatch):
     from uglad_amd import main
 
-    monkeypatch.setattr(main, "_recovered_graph_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._recovered_graph_host", no_host)
     _check_golden(70)
 
 
@@ -364,7 +364,7 @@ def test_emulated_routing_and_argument_errors_of_the_python_surface(emul, monkey
     keep = rho[iu] > a
     assert keep.sum() == 9 and len(strings) == 9 and G.has_edge(names[i], names[j])
     assert strings == [f"({names[p]}, {names[q]}, {round(rho[p, q], 5)}, green)" for p, q in zip(iu[0][keep], iu[1][keep])]
-    monkeypatch.setattr(main, "_recovered_graph_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._recovered_graph_host", no_host)
     with pytest.raises(AssertionError, match="host formulation"):
         main.graph_from_partial_correlations(rho, names, sparsity=10 / E + 1e-9, PLOT=False)
     exact = rho.astype(np.float32).astype(np.float64)
@@ -405,7 +405,7 @@ def test_emulated_drawing_and_disconnected_statistics(emul, tmp_path):
 def test_gpu_matches_the_reference_golden(monkeypatch, D):
     from uglad_amd import main
 
-    monkeypatch.setattr(main, "_recovered_graph_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._recovered_graph_host", no_host)
     _check_golden(D)
 
 
@@ -457,7 +457,7 @@ def test_gpu_fit_at_288_recovers_the_graph_on_the_device(monkeypatch):
     from uglad_amd import main
     from uglad_amd.utils.prepare_data import get_data
 
-    monkeypatch.setattr(main, "_recovered_graph_host", no_host)
+    monkeypatch.setattr("uglad_amd.after._recovered_graph_host", no_host)
     X, _ = get_data(288, (0.02, 0.04), 600, 1, eig_offset=1.0, rng=11)
     est = uglad_amd.uGLAD_GL()
     with pytest.raises(ValueError, match="call fit"):

@@ -212,9 +212,8 @@ def test_emulated_routing_needs_no_host(emul, monkeypatch):
     """main's routing (the library's eigensolver limit lowered so that D = 70 counts as wide): the report stays on the device."""
     from uglad_amd import main
 
-    monkeypatch.setattr(main, "report_metrics_all", no_host)
+    monkeypatch.setattr("uglad_amd.after.report_metrics_all", no_host)
     monkeypatch.setattr(emul, "max_eig_dim", 32)
-    monkeypatch.setattr(main, "WIDE_METRICS_MIN_DIM", 0)  # (the measured threshold concerns the GPU, not the routing under test)
     T, G = pairs(2, 70, seed=75)
     got = main.device_report_metrics(T, G)
     ref = reference(T, G)
@@ -256,7 +255,7 @@ def test_emulated_matches_the_reference_golden(emul, monkeypatch):
     """The golden through main's routing on the emulator (its build's eigensolver stops at D = 160, so D = 288 is wide there too)."""
     from uglad_amd import main
 
-    monkeypatch.setattr(main, "report_metrics_all", no_host)
+    monkeypatch.setattr("uglad_amd.after.report_metrics_all", no_host)
     _check_golden()
 
 
@@ -265,7 +264,7 @@ def test_emulated_matches_the_reference_golden(emul, monkeypatch):
 def test_gpu_matches_the_reference_golden(monkeypatch):
     from uglad_amd import main
 
-    monkeypatch.setattr(main, "report_metrics_all", no_host)
+    monkeypatch.setattr("uglad_amd.after.report_metrics_all", no_host)
     _check_golden()
 
 
@@ -309,7 +308,7 @@ def test_gpu_fit_at_288_reports_from_the_device(monkeypatch):
     from uglad_amd.utils.metrics import report_metrics_all
     from uglad_amd.utils.prepare_data import get_data
 
-    monkeypatch.setattr(main, "report_metrics_all", no_host)
+    monkeypatch.setattr("uglad_amd.after.report_metrics_all", no_host)
     X, P = get_data(288, (0.02, 0.04), 600, 1, eig_offset=1.0, rng=11)
     est = uglad_amd.uGLAD_GL()
     res = est.fit(X[0], true_theta=P[0], epochs=2, lr=0.01, L=3, verbose=False)

@@ -127,20 +127,25 @@ def batch_symeig(A: Tensor):
     return beta, U
 
 
-class _GladUnrolled(torch.autograd.Function):
+class _GladPass(torch.autograd.Function):
+    """G independent GLAD problems in ONE batch: group g owns matrices [g M/G, (g+1) M/G), params[g] (42 floats) and its own lambda
+    sequence (uglad_glad_forward_grouped / uglad_glad_backward_grouped).  `glad()` is G = 1, for which HipLib picks the ungrouped entry
+    points -- its (L+1, 1) lambdas and (1, 42) gradient are the bytes of their (L+1,) and (42,) -- and the only case that can be sharded
+    over ranks (`coll`, `m_global`)."""
+
     @staticmethod
     def forward(ctx, S: Tensor, params: Tensor, L: int, init_diag: int, lambda_init: float, mode: int,
                 coll: Collective, m_global: int):
         lib = _lib.get_lib()
         M, D, _ = S.shape
-        dev = S.device
+        G = params.shape[0]
         train = ctx.needs_input_grad[1] or ctx.needs_input_grad[0]  # (the backward pass with respect to S needs the same state)
-        f32 = dict(dtype=torch.float32, device=dev)
+        f32 = dict(dtype=torch.float32, device=S.device)
         params = params.detach().contiguous()
-        lam = torch.empty(L + 1, **f32)
-        lam_in = torch.empty(L + 1, 2, **f32)
+        lam = torch.empty(L + 1, G, **f32)
+        lam_in = torch.empty(L + 1, G, 2, **f32)
         nf_partial = torch.empty(M, **f32)
-        nf_sum = torch.empty(1, **f32)
+        nf_sum = torch.empty(G, **f32)
         cond = torch.zeros(M, **f32) if _monitors else None  # regime diagnostic: only when somebody listens
         if train:
             Z = torch.empty(L + 1, M, D, D, **f32)
@@ -149,30 +154,28 @@ class _GladUnrolled(torch.autograd.Function):
             beta = torch.empty(L, M, D, **f32)
         else:
             Z = torch.empty(2, M, D, D, **f32)
+            half = U = beta = None
         wsp = lib.workspace(M, D, S)
+        state = (Z, half, U, beta, lam, lam_in, nf_partial, nf_sum, wsp, mode)
         fused = type(coll) is Collective and m_global == M  # plain single-process run: nothing to exchange between steps
         native = None if fused else getattr(coll, "native_exchange", lambda: None)()
-        if native is not None:
-            # sharded over RCCL: the whole pass in one library call, ncclAllReduce of the per-step scalar issued from C on this stream
-            lib.glad_forward_sharded(S, params, lambda_init, init_diag, L, Z, half if train else None, U if train else None,
-                                     beta if train else None, lam, lam_in, nf_partial, nf_sum, wsp, mode, m_global, native,
-                                     cond_max=cond)
-            fused = True
-        elif fused:
+        if fused:
             # one library call enqueues the whole pass (no per-step Python between the launches)
-            lib.glad_forward(S, params, lambda_init, init_diag, L, Z, half if train else None, U if train else None,
-                             beta if train else None, lam, lam_in, nf_partial, nf_sum, wsp, mode, cond_max=cond)
+            lib.glad_forward(S, params, lambda_init, init_diag, L, *state, groups=G, cond_max=cond)
+        elif native is not None:
+            # sharded over RCCL: the whole pass in one library call, ncclAllReduce of the per-step scalar issued from C on this stream
+            lib.glad_forward_sharded(S, params, lambda_init, init_diag, L, *state, m_global, native, cond_max=cond)
         else:
+            # sharded over an injected collective: one exchange of the batch-wide norm per step, from Python
             lib.init_theta(S, params, init_diag, Z[0], wsp)
-            lib.lambda_init(params, lambda_init, lam[0:1], lam_in[0])
-        inv_m = 1.0 / float(m_global)
-        for k in range(0 if fused else L):
-            zi, zo = (Z[k], Z[k + 1]) if train else (Z[k & 1], Z[(k + 1) & 1])
-            lib.cell_fwd(S, zi, lam[k:k + 1], params, zo, half[k] if train else None, U[k] if train else None,
-                         beta[k] if train else None, nf_partial, wsp, mode, cond_max=cond)
-            lib.sum_partials(nf_partial, nf_sum)
-            coll.all_reduce_sum(nf_sum)
-            lib.lambda_step(nf_sum, inv_m, lam[k:k + 1], params, lam[k + 1:k + 2], lam_in[k + 1])
+            lib.lambda_init(params, lambda_init, lam[0], lam_in[0])
+            for k in range(L):
+                zi, zo = (Z[k], Z[k + 1]) if train else (Z[k & 1], Z[(k + 1) & 1])
+                lib.cell_fwd(S, zi, lam[k], params, zo, half[k] if train else None, U[k] if train else None,
+                             beta[k] if train else None, nf_partial, wsp, mode, cond_max=cond)
+                lib.sum_partials(nf_partial, nf_sum)
+                coll.all_reduce_sum(nf_sum)
+                lib.lambda_step(nf_sum, 1.0 / float(m_global), lam[k], params, lam[k + 1], lam_in[k + 1])
         out = (Z[L] if train else Z[L & 1]).clone()
         if cond is not None:
             ub = lib.cond_is_upper_bound(M, D, train, mode)
@@ -185,32 +188,41 @@ class _GladUnrolled(torch.autograd.Function):
         return out, lam
 
     @staticmethod
-    def backward(ctx, G: Tensor, _glam):
+    def backward(ctx, Gout: Tensor, _glam):
         lib = _lib.get_lib()
         S, params, Z, half, U, beta, lam, lam_in = ctx.saved_tensors
         L, init_diag, mode = ctx.cfg
         M, D, _ = S.shape
+        G = params.shape[0]
         f32 = dict(dtype=torch.float32, device=S.device)
         bufs = (torch.empty(M, D, D, **f32), torch.empty(M, D, D, **f32))
         grad_rho_partial = torch.empty(M, _lib.NRHO, **f32)
         glam_partial = torch.empty(L, M, **f32)
         gt_partial = torch.empty(M, **f32)
-        grad = torch.empty(_lib.NPARAM, **f32)
+        grad = torch.empty(G, _lib.NPARAM, **f32)
         wsp = lib.workspace(M, D, S)  # read by the beyond-LDS instantiations (D > 128) only
         # dL/dS (symmetric part, include/uglad_hip.h) when S needs it: S is local to the rank, so a sharded pass exchanges nothing for it
         gS = torch.empty(M, D, D, **f32) if ctx.needs_input_grad[0] else None
         # the parameter gradients are sums over the LOCAL matrices; a sharded caller all-reduces them (uglad_amd/dist.py)
-        lib.glad_backward(G.contiguous(), S, params, init_diag, L, Z, half, U, beta, lam, lam_in, bufs[0], bufs[1],
-                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, gS=gS)
+        lib.glad_backward(Gout.contiguous(), S, params, init_diag, L, Z, half, U, beta, lam, lam_in, bufs[0], bufs[1],
+                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, groups=G, gS=gS)
         return gS, grad if ctx.needs_input_grad[1] else None, None, None, None, None, None, None
 
 
-def _input_covariance(Sb: Tensor, device) -> Tensor:
-    """Sb as the kernels take it (contiguous fp32 on `device`); kept in the autograd graph when it requires grad and grad mode is on,
-    detached otherwise."""
+def _run_pass(Sb: Tensor, params: Tensor, lambda_init, L, INIT_DIAG, sqrt_mode: Optional[str], coll: Collective, m_global: int):
+    """(Theta, lambdas (L+1, G)) of one pass over Sb (M, D, D) with params (G, 42), after the checks both callers share.  Sb goes in as
+    the kernels take it (contiguous fp32 on the parameters' device): kept in the autograd graph when it requires grad and grad mode is
+    on, detached otherwise."""
+    if sqrt_mode is None:
+        sqrt_mode = DEFAULT_SQRT_MODE
+    if sqrt_mode not in _lib.SQRT_MODES:
+        raise ValueError(f"sqrt_mode must be one of {sorted(_lib.SQRT_MODES)}")
+    if INIT_DIAG not in (0, 1):
+        raise ValueError("INIT_DIAG must be 0 or 1")
     if not (Sb.requires_grad and torch.is_grad_enabled()):
         Sb = Sb.detach()
-    return Sb.to(device=device, dtype=torch.float32).contiguous()
+    Sb = Sb.to(device=params.device, dtype=torch.float32).contiguous()
+    return _GladPass.apply(Sb, params, int(L), int(INIT_DIAG), float(lambda_init), _lib.SQRT_MODES[sqrt_mode], coll, m_global)
 
 
 def glad(
@@ -235,83 +247,15 @@ def glad(
     part (G + G^T) / 2 of the reference's gradient G, in Sb's dtype and on its device (include/uglad_hip.h,
     uglad_glad_backward_wrt_s), on every backward path.  Otherwise Sb is detached as before.
     """
-    if sqrt_mode is None:
-        sqrt_mode = DEFAULT_SQRT_MODE
-    if sqrt_mode not in _lib.SQRT_MODES:
-        raise ValueError(f"sqrt_mode must be one of {sorted(_lib.SQRT_MODES)}")
-    if INIT_DIAG not in (0, 1):
-        raise ValueError("INIT_DIAG must be 0 or 1")
     if Sb.dim() == 2:
         Sb = Sb.reshape(1, Sb.shape[0], Sb.shape[1])
-    params = model.packed()
-    Sb = _input_covariance(Sb, params.device)
     coll = collective if collective is not None else get_collective()
     if global_batch is None and coll.world_size > 1:
         # (the shards of a batch that does not divide evenly differ in size: the divisor of the batch mean cannot be guessed locally)
         raise ValueError("glad(): a sharded batch needs global_batch = the number of matrices over all ranks")
     m_global = int(global_batch) if global_batch is not None else Sb.shape[0]
-    theta, lam = _GladUnrolled.apply(Sb, params, int(L), int(INIT_DIAG), float(lambda_init), _lib.SQRT_MODES[sqrt_mode],
-                                     coll, m_global)
-    return (theta, lam) if return_lambdas else theta
-
-
-# ------------------------------------------------------------------------------------------------ grouped passes (SURVEY 8f N2)
-class _GladGrouped(torch.autograd.Function):
-    """G independent GLAD problems in ONE batch: group g owns matrices [g M/G, (g+1) M/G), params[g] (42 floats) and its
-    own lambda sequence (uglad_glad_forward_grouped / uglad_glad_backward_grouped)."""
-
-    @staticmethod
-    def forward(ctx, S: Tensor, params: Tensor, L: int, init_diag: int, lambda_init: float, mode: int):
-        lib = _lib.get_lib()
-        M, D, _ = S.shape
-        G = params.shape[0]
-        train = ctx.needs_input_grad[1] or ctx.needs_input_grad[0]
-        f32 = dict(dtype=torch.float32, device=S.device)
-        params = params.detach().contiguous()
-        lam = torch.empty(L + 1, G, **f32)
-        lam_in = torch.empty(L + 1, G, 2, **f32)
-        nf_partial = torch.empty(M, **f32)
-        nf_sum = torch.empty(G, **f32)
-        if train:
-            Z = torch.empty(L + 1, M, D, D, **f32)
-            half = torch.empty(L, M, D, D, **f32)
-            U = torch.empty(L, M, D, D, **f32)
-            beta = torch.empty(L, M, D, **f32)
-        else:
-            Z = torch.empty(2, M, D, D, **f32)
-            half = U = beta = None
-        wsp = lib.workspace(M, D, S)
-        cond = torch.zeros(M, **f32) if _monitors else None
-        lib.glad_forward(S, params, lambda_init, init_diag, L, Z, half, U, beta, lam, lam_in, nf_partial, nf_sum, wsp, mode,
-                         groups=G, cond_max=cond)
-        if cond is not None:
-            ub = lib.cond_is_upper_bound(M, D, train, mode)
-            for mon in list(_monitors):
-                mon.report(cond, upper_bound=ub)
-        out = (Z[L] if train else Z[L & 1]).clone()
-        if train:
-            ctx.save_for_backward(S, params, Z, half, U, beta, lam, lam_in)
-            ctx.cfg = (L, init_diag, mode)
-        return out
-
-    @staticmethod
-    def backward(ctx, Gout: Tensor):
-        lib = _lib.get_lib()
-        S, params, Z, half, U, beta, lam, lam_in = ctx.saved_tensors
-        L, init_diag, mode = ctx.cfg
-        M, D, _ = S.shape
-        G = params.shape[0]
-        f32 = dict(dtype=torch.float32, device=S.device)
-        bufs = (torch.empty(M, D, D, **f32), torch.empty(M, D, D, **f32))
-        grad_rho_partial = torch.empty(M, _lib.NRHO, **f32)
-        glam_partial = torch.empty(L, M, **f32)
-        gt_partial = torch.empty(M, **f32)
-        grad = torch.empty(G, _lib.NPARAM, **f32)
-        wsp = lib.workspace(M, D, S)
-        gS = torch.empty(M, D, D, **f32) if ctx.needs_input_grad[0] else None
-        lib.glad_backward(Gout.contiguous(), S, params, init_diag, L, Z, half, U, beta, lam, lam_in, bufs[0], bufs[1],
-                          grad_rho_partial, glam_partial, gt_partial, grad, wsp, mode, groups=G, gS=gS)
-        return gS, grad if ctx.needs_input_grad[1] else None, None, None, None, None
+    theta, lam = _run_pass(Sb, model.packed()[None], lambda_init, L, INIT_DIAG, sqrt_mode, coll, m_global)
+    return (theta, lam[:, 0]) if return_lambdas else theta
 
 
 def glad_grouped(Sb: Tensor, params: Tensor, lambda_init: float = 1, L: int = 15, INIT_DIAG: int = 0,
@@ -319,13 +263,6 @@ def glad_grouped(Sb: Tensor, params: Tensor, lambda_init: float = 1, L: int = 15
     """`glad` for G independent problems at once: Sb (M, D, D) with M a multiple of G = params.shape[0]; params (G, 42) in the
     packed layout of GladParams.packed() (include/uglad_hip.h).  Group g = matrices [g M/G, (g+1) M/G): its own parameters,
     its own batch norm and lambda sequence -- exactly what G separate `glad` calls would compute."""
-    if sqrt_mode is None:
-        sqrt_mode = DEFAULT_SQRT_MODE
-    if sqrt_mode not in _lib.SQRT_MODES:
-        raise ValueError(f"sqrt_mode must be one of {sorted(_lib.SQRT_MODES)}")
-    if INIT_DIAG not in (0, 1):
-        raise ValueError("INIT_DIAG must be 0 or 1")
     if params.dim() != 2 or params.shape[1] != _lib.NPARAM or Sb.dim() != 3 or Sb.shape[0] % params.shape[0] != 0:
         raise ValueError("params must be (G, 42) and Sb (M, D, D) with M a multiple of G")
-    Sb = _input_covariance(Sb, params.device)  # (in the graph when it requires grad: as in glad())
-    return _GladGrouped.apply(Sb, params, int(L), int(INIT_DIAG), float(lambda_init), _lib.SQRT_MODES[sqrt_mode])
+    return _run_pass(Sb, params, lambda_init, L, INIT_DIAG, sqrt_mode, Collective(), Sb.shape[0])[0]

@@ -39,6 +39,15 @@ class GladParams(nn.Module):
         """The (42,) vector the kernels read; differentiable w.r.t. the 11 parameters (include/uglad_hip.h layout)."""
         return torch.cat([p.reshape(-1) for p in self.parameters()])
 
+    def load_packed_(self, flat: Tensor, grads: bool = False) -> None:
+        """Inverse of packed(): the first 42 entries of `flat` go into the 11 parameters, or with `grads` into their .grad."""
+        with torch.no_grad():
+            off = 0
+            for p in self.parameters():
+                n = p.numel()
+                (p.grad if grads else p).copy_(flat[off:off + n].reshape(p.shape))
+                off += n
+
     # ---- API parity with the reference (not on the hot path)
     def eta_forward(self, X: Tensor, S: Tensor, k: int, F3: Tensor = None) -> Tensor:
         feats = [X.reshape(X.shape[0], -1, 1), S.expand_as(X).reshape(X.shape[0], -1, 1)]

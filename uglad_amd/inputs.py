@@ -1,0 +1,134 @@
+"""How a table becomes the matrix the path runs on: the covariance (host fp64 like the reference's prepare_data.get_covariance, or under
+`device_covariance` the device front-ends uglad_covariance / uglad_covariance_wide), the association matrix of a mixed table
+(uglad_association) and the rank correlations of the nonparanormal model (uglad_rank_correlation).  `uglad_amd.main` re-exports the
+public names."""
+from __future__ import annotations
+
+import contextlib
+
+import numpy as np
+import torch
+
+from . import _lib
+from .utils import prepare_data
+
+
+_NUMPY_DTYPE = {torch.float32: np.float32, torch.float64: np.float64}
+
+
+def _to_dev(a, dtype=torch.float32) -> torch.Tensor:
+    """`a` (array or tensor) as a contiguous, detached tensor of `dtype` on the library's device.  A device tensor is converted on the
+    device; a host array is converted on the host and uploaded once (a read-only one is copied first: torch.from_numpy wants to write)."""
+    if torch.is_tensor(a):
+        return a.detach().to(device=_lib.device(), dtype=dtype).contiguous()
+    a = np.ascontiguousarray(a, dtype=_NUMPY_DTYPE[dtype])
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(_lib.device())
+
+
+_DEVICE_COVARIANCE = False  # set for the duration of a fit()/predict() by uGLAD_GL / uGLAD_multitask(device_covariance=True)
+
+
+@contextlib.contextmanager
+def device_covariance(enabled: bool = True):
+    """Within this context the drivers form the covariances (and the reference's eigenvalue repair) on the GPU
+    (`uglad_covariance`, beyond the eigensolver's size `uglad_covariance_wide`) instead of in fp64 numpy on the host
+    (prepare_data.py:328-356)."""
+    global _DEVICE_COVARIANCE
+    saved, _DEVICE_COVARIANCE = _DEVICE_COVARIANCE, bool(enabled)
+    try:
+        yield
+    finally:
+        _DEVICE_COVARIANCE = saved
+
+
+REPAIR_THRESHOLD = 1e-6  # prepare_data.py:347: "min eig <= 1e-6 -> S += (offset - min eig) I"
+REPAIR_BAND = 1e-4       # fp32 eigenvalues within this (relative to ||S||_2-ish scale) of the threshold are re-decided in fp64
+
+
+def _device_covariance_group(X: np.ndarray, eval_offset: float) -> torch.Tensor:
+    """(K, N, D) equally-shaped tables -> (K, D, D) repaired covariances on the device.
+
+    The reference decides its repair from fp64 eigenvalues (prepare_data.py:343-352); the device sees fp32 eigenvalues of an
+    fp32 covariance, whose absolute error is ~1e-7 ||S||.  Where the device's smallest eigenvalue lies within REPAIR_BAND of
+    the threshold the decision could flip -- an O(offset) discontinuity -- so exactly those matrices (rare: nearly singular
+    with a minimum eigenvalue of ~1e-6) are re-decided from an fp64 eigvalsh on the host and corrected in place.
+    Tables wider than the eigensolver's size go to the fp64 front-end, which needs no such band."""
+    lib = _lib.get_lib()
+    if X.shape[-1] > lib.max_eig_dim:
+        # beyond the eigensolver's size: the fp64 front-end (csrc/cov_wide.h) takes the reference's decision itself, in fp64
+        return lib.covariance_wide(_to_dev(X, torch.float64), normalize=False, eval_offset=eval_offset, repair=True)
+    S, mn = lib.covariance(_to_dev(X), normalize=False, eval_offset=eval_offset, repair=True, return_min_eig=True)
+    mn = mn.cpu().numpy().astype(np.float64)
+    scale = np.maximum(1.0, S.diagonal(dim1=1, dim2=2).abs().sum(1).cpu().numpy())  # trace >= ||S||_2 for a PSD matrix
+    for k in np.nonzero(np.abs(mn - REPAIR_THRESHOLD) <= REPAIR_BAND * scale)[0]:
+        applied = mn[k] <= REPAIR_THRESHOLD
+        Sk = S[k].double().cpu().numpy()
+        if applied:
+            Sk = Sk - (eval_offset - mn[k]) * np.eye(Sk.shape[0])  # undo the device's shift, decide again
+        mn64 = float(np.linalg.eigvalsh(0.5 * (Sk + Sk.T)).min())
+        if mn64 <= REPAIR_THRESHOLD:
+            Sk = Sk + (eval_offset - mn64) * np.eye(Sk.shape[0])
+        S[k] = torch.from_numpy(Sk.astype(np.float32)).to(S.device)
+    return S
+
+
+def _covariance(Xb, eval_offset):
+    """Tables (K,N,D) -> (K,D,D) fp32 covariances on the device, repaired as prepare_data.get_covariance does.
+    Under device_covariance the tables are grouped by shape (missing mode's row-subsampled folds and multitask tables may
+    differ in length) and every group of equal shape is one launch of the device front-end."""
+    if _DEVICE_COVARIANCE:
+        tables = [np.asarray(x) for x in Xb]
+        max_dim = _lib.get_lib().max_dim  # (what the cell covers; wider tables take the host path below, and fail at the cell)
+        if tables and all(t.ndim == 2 and t.shape[1] <= max_dim and t.dtype != object for t in tables):
+            groups = {}
+            for i, t in enumerate(tables):
+                groups.setdefault(t.shape, []).append(i)
+            D = tables[0].shape[1]
+            if all(shape[1] == D for shape in groups):
+                out = torch.empty(len(tables), D, D, dtype=torch.float32, device=_lib.device())
+                for idx in groups.values():
+                    out[idx] = _device_covariance_group(np.stack([tables[i] for i in idx]), eval_offset)
+                return out
+    return _to_dev(prepare_data.get_covariance(Xb, offset=eval_offset))
+
+
+def mixed_association(df, dtype, repair: bool = True, eval_offset: float = 0.1):
+    """The association matrix of a table that mixes categorical ('c') and real ('r') columns, on the device (uglad_association,
+    csrc/assoc_wide.h; the reference's pairwise_cov_matrix, prepare_data.py:253-285): `dtype` maps column name -> 'c' | 'r'.  Returns
+    (A, min_eig): A the (D, D) fp32 matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset -
+    min eig) I, prepare_data.py:347-352), and min_eig the smallest eigenvalue before the repair as a float (+inf where none was needed;
+    None without `repair`)."""
+    table, maps = prepare_data.encode_mixed_table(df, dtype)
+    A, mn, _ = _lib.get_lib().association(torch.from_numpy(table[None]).to(_lib.device()), maps, eval_offset=eval_offset, repair=repair)
+    return A[0], (None if mn is None else float(mn[0]))
+
+
+def _rank_tables(X):
+    """(tables (K, N, D) float64 contiguous, single, names): an (N, D) array or DataFrame, or a list / (K, N, D) array of tables."""
+    names = [str(c) for c in X.columns] if hasattr(X, "columns") else None
+    single = hasattr(X, "columns") or (not isinstance(X, (list, tuple)) and np.ndim(X) == 2)
+    tables = np.array(X, dtype=np.float64, order="C")  # (a copy of its own: the caller's array may be read-only)
+    tables = tables[None] if single else tables
+    if tables.ndim != 3:
+        raise ValueError("rank_correlation takes an (N, D) table, or a list / (K, N, D) array of tables of one shape")
+    if np.isnan(tables).any():
+        raise ValueError("rank_correlation: the table holds NaN; impute or drop those rows first")
+    return tables, single, names
+
+
+def rank_correlation(X, method: str = "kendall", transform: bool = True, repair: bool = True, eval_offset: float = 0.1):
+    """The rank-based correlation matrix of the nonparanormal (Gaussian copula) model, on the device (uglad_rank_correlation,
+    csrc/rank_wide.h; additive, what R's huge.npn offers): `method` "spearman" (with `transform` 2 sin(pi rho / 6)), "kendall" (tau-b,
+    sin(pi tau / 2): the SKEPTIC estimator) or "scores" (the correlation of Phi^-1(rank / (N + 1))).  X is an (N, D) array or DataFrame,
+    or a list / (K, N, D) array of tables of one shape.  Returns (A, min_eig) like mixed_association: A the (D, D) -- or (K, D, D) -- fp32
+    matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset - min eig) I), and min_eig the
+    smallest eigenvalue before the repair as a float -- or a (K,) float64 array -- (+inf where none was needed; None without `repair`).
+    A constant column gives NaN in its row and column; a NaN raises ValueError."""
+    tables, single, _ = _rank_tables(X)
+    out = _lib.get_lib().rank_correlation(torch.from_numpy(tables).to(_lib.device()), method, transform=transform,
+                                          eval_offset=eval_offset, repair=repair)
+    mn = None if out.min_eig is None else out.min_eig.cpu().numpy()
+    if single:
+        return out.A[0], (None if mn is None else float(mn[0]))
+    return out.A, mn
+

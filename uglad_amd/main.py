@@ -10,39 +10,53 @@ instead of sys.exit(0) (main.py:137,667,708); epochs < 10 works (the reference d
 plotted (main.py:416 writes ./loss_curve.png); tensors live on the GPU until `fit` stores numpy attributes.  Additive
 only: `sqrt_mode=`, `predict()`, and sharding of the multi-task / missing-data batch over the ranks of an initialised
 torch.distributed process group (one process per GPU, RCCL).
+
+How a table becomes the input matrix lives in `inputs.py`, everything after the path (the reference's main.py:796-1300) in `after.py`;
+their public names are imported here, so `uglad_amd.main.X` resolves as it does in the reference.
 """
 from __future__ import annotations
 
-import contextlib
 import copy
 from time import time
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from .after import (  # noqa: F401  (everything after the path: uglad_amd/after.py)
+    GRAPH_STAT_KEYS, METRIC_KEYS, RecoveredGraph, SampleScores, _to_model_coordinates, compute_graph_statistics, compute_map_estimate,
+    conditional_gaussian_batch, conditional_gaussian_with_probabilities, device_report_metrics, get_partial_correlations,
+    graph_from_partial_correlations, recovered_graph, sample_scores)
 from .dist import Collective, get_collective
 from .glad import glad
 from .glad.glad_params import GladParams
+from .inputs import (  # noqa: F401  (how a table becomes the input matrix: uglad_amd/inputs.py)
+    _covariance, _rank_tables, _to_dev, device_covariance, mixed_association, rank_correlation)
 from .utils import prepare_data
 from .utils.metrics import report_metrics_all  # noqa: F401  (host-side API parity; the drivers count on the device)
 
 
 # ============================================================================================ loss
+def _loss_forward(theta: torch.Tensor, S: torch.Tensor, struct: Optional[torch.Tensor]):
+    """uglad_loss_fwd on contiguous theta (M, D, D): (the M terms -logdet Theta_b + tr(S_b Theta_b) [+ penalty], Theta^-1)."""
+    lib = _lib.get_lib()
+    M, D, _ = theta.shape
+    partial = torch.empty(M, dtype=torch.float32, device=theta.device)
+    theta_inv = torch.empty_like(theta)
+    wsp = lib.workspace(M, D, theta)
+    lib.loss_fwd(theta, S, struct, partial, theta_inv, wsp)
+    return partial, theta_inv
+
+
 class _GlassoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, S, struct, divisor):
-        lib = _lib.get_lib()
-        M, D, _ = theta.shape
         f32 = dict(dtype=torch.float32, device=theta.device)
         theta = theta.contiguous()
-        partial = torch.empty(M, **f32)
-        theta_inv = torch.empty(M, D, D, **f32)
-        wsp = lib.workspace(M, D, theta)
-        lib.loss_fwd(theta, S, struct, partial, theta_inv, wsp)
+        partial, theta_inv = _loss_forward(theta, S, struct)
         total = torch.empty(1, **f32)
-        lib.sum_partials(partial, total)
+        _lib.get_lib().sum_partials(partial, total)
         ctx.save_for_backward(theta, theta_inv, S, struct if struct is not None else torch.empty(0, **f32))
         ctx.has_struct = struct is not None
         ctx.scale = 1.0 / float(divisor)
@@ -93,15 +107,8 @@ def loss_uGLAD(theta: torch.Tensor, S: torch.Tensor, struct_theta: Optional[torc
 def _loss_per_matrix(theta: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
     """-logdet Theta_b + tr(S_b Theta_b) for every matrix of the batch, (M,) on the device, no autograd (the test-fold losses
     of the batched CV driver)."""
-    lib = _lib.get_lib()
-    M, D, _ = theta.shape
     theta = theta.detach().contiguous()
-    S = S.detach().to(device=theta.device, dtype=torch.float32).contiguous()
-    partial = torch.empty(M, dtype=torch.float32, device=theta.device)
-    theta_inv = torch.empty_like(theta)
-    wsp = lib.workspace(M, D, theta)
-    lib.loss_fwd(theta, S, None, partial, theta_inv, wsp)
-    return partial
+    return _loss_forward(theta, S.detach().to(device=theta.device, dtype=torch.float32).contiguous(), None)[0]
 
 
 # ============================================================================================ model / forward
@@ -128,120 +135,6 @@ def forward_uGLAD(Sb, model_glad, L: int = 15, INIT_DIAG: int = 0, loss_Sb=None,
     return predTheta, loss
 
 
-def _to_dev(x):
-    return prepare_data.convert_to_torch(x, req_grad=False, device=_lib.device())
-
-
-_DEVICE_COVARIANCE = False  # set for the duration of a fit()/predict() by uGLAD_GL / uGLAD_multitask(device_covariance=True)
-
-
-@contextlib.contextmanager
-def device_covariance(enabled: bool = True):
-    """Within this context the drivers form the covariances (and the reference's eigenvalue repair) on the GPU
-    (`uglad_covariance`, beyond the eigensolver's size `uglad_covariance_wide`) instead of in fp64 numpy on the host
-    (prepare_data.py:328-356)."""
-    global _DEVICE_COVARIANCE
-    saved, _DEVICE_COVARIANCE = _DEVICE_COVARIANCE, bool(enabled)
-    try:
-        yield
-    finally:
-        _DEVICE_COVARIANCE = saved
-
-
-REPAIR_THRESHOLD = 1e-6  # prepare_data.py:347: "min eig <= 1e-6 -> S += (offset - min eig) I"
-REPAIR_BAND = 1e-4       # fp32 eigenvalues within this (relative to ||S||_2-ish scale) of the threshold are re-decided in fp64
-
-
-def _device_covariance_group(X: np.ndarray, eval_offset: float) -> torch.Tensor:
-    """(K, N, D) equally-shaped tables -> (K, D, D) repaired covariances on the device.
-
-    The reference decides its repair from fp64 eigenvalues (prepare_data.py:343-352); the device sees fp32 eigenvalues of an
-    fp32 covariance, whose absolute error is ~1e-7 ||S||.  Where the device's smallest eigenvalue lies within REPAIR_BAND of
-    the threshold the decision could flip -- an O(offset) discontinuity -- so exactly those matrices (rare: nearly singular
-    with a minimum eigenvalue of ~1e-6) are re-decided from an fp64 eigvalsh on the host and corrected in place.
-    Tables wider than the eigensolver's size go to the fp64 front-end, which needs no such band."""
-    lib = _lib.get_lib()
-    if X.shape[-1] > lib.max_eig_dim:
-        # beyond the eigensolver's size: the fp64 front-end (csrc/cov_wide.h) takes the reference's decision itself, in fp64
-        return lib.covariance_wide(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(_lib.device()), normalize=False,
-                                   eval_offset=eval_offset, repair=True)
-    Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.device())
-    S, mn = lib.covariance(Xd, normalize=False, eval_offset=eval_offset, repair=True, return_min_eig=True)
-    mn = mn.cpu().numpy().astype(np.float64)
-    scale = np.maximum(1.0, S.diagonal(dim1=1, dim2=2).abs().sum(1).cpu().numpy())  # trace >= ||S||_2 for a PSD matrix
-    for k in np.nonzero(np.abs(mn - REPAIR_THRESHOLD) <= REPAIR_BAND * scale)[0]:
-        applied = mn[k] <= REPAIR_THRESHOLD
-        Sk = S[k].double().cpu().numpy()
-        if applied:
-            Sk = Sk - (eval_offset - mn[k]) * np.eye(Sk.shape[0])  # undo the device's shift, decide again
-        mn64 = float(np.linalg.eigvalsh(0.5 * (Sk + Sk.T)).min())
-        if mn64 <= REPAIR_THRESHOLD:
-            Sk = Sk + (eval_offset - mn64) * np.eye(Sk.shape[0])
-        S[k] = torch.from_numpy(Sk.astype(np.float32)).to(S.device)
-    return S
-
-
-def _covariance(Xb, eval_offset):
-    """Tables (K,N,D) -> (K,D,D) fp32 covariances on the device, repaired as prepare_data.get_covariance does.
-    Under device_covariance the tables are grouped by shape (missing mode's row-subsampled folds and multitask tables may
-    differ in length) and every group of equal shape is one launch of the device front-end."""
-    if _DEVICE_COVARIANCE:
-        tables = [np.asarray(x) for x in Xb]
-        max_dim = _lib.get_lib().max_dim  # (what the cell covers; wider tables take the host path below, and fail at the cell)
-        if tables and all(t.ndim == 2 and t.shape[1] <= max_dim and t.dtype != object for t in tables):
-            groups = {}
-            for i, t in enumerate(tables):
-                groups.setdefault(t.shape, []).append(i)
-            D = tables[0].shape[1]
-            if all(shape[1] == D for shape in groups):
-                out = torch.empty(len(tables), D, D, dtype=torch.float32, device=_lib.device())
-                for idx in groups.values():
-                    out[idx] = _device_covariance_group(np.stack([tables[i] for i in idx]), eval_offset)
-                return out
-    return _to_dev(prepare_data.get_covariance(Xb, offset=eval_offset))
-
-
-def mixed_association(df, dtype, repair: bool = True, eval_offset: float = 0.1):
-    """The association matrix of a table that mixes categorical ('c') and real ('r') columns, on the device (uglad_association,
-    csrc/assoc_wide.h; the reference's pairwise_cov_matrix, prepare_data.py:253-285): `dtype` maps column name -> 'c' | 'r'.  Returns
-    (A, min_eig): A the (D, D) fp32 matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset -
-    min eig) I, prepare_data.py:347-352), and min_eig the smallest eigenvalue before the repair as a float (+inf where none was needed;
-    None without `repair`)."""
-    table, maps = prepare_data.encode_mixed_table(df, dtype)
-    A, mn, _ = _lib.get_lib().association(torch.from_numpy(table[None]).to(_lib.device()), maps, eval_offset=eval_offset, repair=repair)
-    return A[0], (None if mn is None else float(mn[0]))
-
-
-def _rank_tables(X):
-    """(tables (K, N, D) float64 contiguous, single, names): an (N, D) array or DataFrame, or a list / (K, N, D) array of tables."""
-    names = [str(c) for c in X.columns] if hasattr(X, "columns") else None
-    single = hasattr(X, "columns") or (not isinstance(X, (list, tuple)) and np.ndim(X) == 2)
-    tables = np.array(X, dtype=np.float64, order="C")  # (a copy of its own: the caller's array may be read-only)
-    tables = tables[None] if single else tables
-    if tables.ndim != 3:
-        raise ValueError("rank_correlation takes an (N, D) table, or a list / (K, N, D) array of tables of one shape")
-    if np.isnan(tables).any():
-        raise ValueError("rank_correlation: the table holds NaN; impute or drop those rows first")
-    return tables, single, names
-
-
-def rank_correlation(X, method: str = "kendall", transform: bool = True, repair: bool = True, eval_offset: float = 0.1):
-    """The rank-based correlation matrix of the nonparanormal (Gaussian copula) model, on the device (uglad_rank_correlation,
-    csrc/rank_wide.h; additive, what R's huge.npn offers): `method` "spearman" (with `transform` 2 sin(pi rho / 6)), "kendall" (tau-b,
-    sin(pi tau / 2): the SKEPTIC estimator) or "scores" (the correlation of Phi^-1(rank / (N + 1))).  X is an (N, D) array or DataFrame,
-    or a list / (K, N, D) array of tables of one shape.  Returns (A, min_eig) like mixed_association: A the (D, D) -- or (K, D, D) -- fp32
-    matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: A += (eval_offset - min eig) I), and min_eig the
-    smallest eigenvalue before the repair as a float -- or a (K,) float64 array -- (+inf where none was needed; None without `repair`).
-    A constant column gives NaN in its row and column; a NaN raises ValueError."""
-    tables, single, _ = _rank_tables(X)
-    out = _lib.get_lib().rank_correlation(torch.from_numpy(tables).to(_lib.device()), method, transform=transform,
-                                          eval_offset=eval_offset, repair=repair)
-    mn = None if out.min_eig is None else out.min_eig.cpu().numpy()
-    if single:
-        return out.A[0], (None if mn is None else float(mn[0]))
-    return out.A, mn
-
-
 def _print_every(EPOCHS: int) -> int:
     return max(1, int(EPOCHS / 10))
 
@@ -252,12 +145,8 @@ def _allreduce_grads(model, loss, coll: Collective):
         return loss.detach()
     flat = torch.cat([p.grad.reshape(-1) for p in model.parameters()] + [loss.detach().reshape(1)])
     coll.all_reduce_sum(flat)
-    off = 0
-    for p in model.parameters():
-        n = p.numel()
-        p.grad.copy_(flat[off:off + n].reshape(p.shape))
-        off += n
-    return flat[off]
+    model.load_packed_(flat, grads=True)
+    return flat[-1]
 
 
 # ============================================================================================ drivers
@@ -280,18 +169,7 @@ def run_uGLAD_direct(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, 
     # asynchronously and is looked at one epoch later; the speculative epoch is then undone (the 42 parameters are snapshotted
     # before every step), which leaves exactly the model the reference returns.
     lagged = Sb.is_cuda
-    params = list(model_glad.parameters())
     pending = None  # (epoch, event, pinned flag, predTheta of that epoch, snapshot taken before that epoch's step)
-
-    def snapshot():  # one launch: the 42 parameters packed (the optimiser is not returned, its state needs no rescue)
-        return torch.cat([p.detach().reshape(-1) for p in params])
-
-    def restore(snap):
-        with torch.no_grad():
-            off = 0
-            for p in params:
-                p.copy_(snap[off:off + p.numel()].reshape(p.shape))
-                off += p.numel()
 
     def nan_epoch(p):
         p[1].synchronize()
@@ -310,7 +188,8 @@ def run_uGLAD_direct(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, 
             flag.copy_(torch.isnan(loss.detach()).reshape(1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            pending = (e, ev, flag, predTheta_e, snapshot())
+            # (the snapshot is one launch: the 42 parameters packed; the optimiser is not returned, its state needs no rescue)
+            pending = (e, ev, flag, predTheta_e, model_glad.packed().detach())
         elif torch.isnan(loss):
             print(f"Warning: NaN loss encountered at epoch {e}. Try updating the parameters and train.")
             predTheta = predTheta_e
@@ -324,7 +203,7 @@ def run_uGLAD_direct(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, 
         stopped = pending  # the very last epoch was the NaN one
     if stopped is not None:
         print(f"Warning: NaN loss encountered at epoch {stopped[0]}. Try updating the parameters and train.")
-        restore(stopped[4])
+        model_glad.load_packed_(stopped[4])
         predTheta = stopped[3]
     compare_theta = None
     if trueTheta is not None and predTheta is not None:
@@ -355,9 +234,8 @@ def _cv_fold(_k, Sb_train, Sb_test, model_glad, optimizer_glad, EPOCHS, INIT_DIA
     and the host can run ahead of the GPU; the selection is the reference's: strictly smaller test loss, snapshot taken
     AFTER this epoch's optimiser step, NaN never wins."""
     one = Collective()
-    params = list(model_glad.parameters())
     best_loss = torch.full((), float("inf"), dtype=torch.float32, device=Sb_train.device)
-    best_state = torch.cat([p.detach().reshape(-1) for p in params])  # the 42 parameters, packed
+    best_state = model_glad.packed().detach()  # the 42 parameters, packed
     PRINT_EVERY = _print_every(EPOCHS)
     for e in range(EPOCHS):
         optimizer_glad.zero_grad()
@@ -370,18 +248,14 @@ def _cv_fold(_k, Sb_train, Sb_test, model_glad, optimizer_glad, EPOCHS, INIT_DIA
             lt = loss_test.reshape(())
             improved = lt < best_loss
             best_loss = torch.where(improved, lt, best_loss)
-            best_state = torch.where(improved, torch.cat([p.reshape(-1) for p in params]), best_state)
+            best_state = torch.where(improved, model_glad.packed(), best_state)
         if not e % PRINT_EVERY and VERBOSE:
             print(f"Fold {_k}: epoch:{e}/{EPOCHS} test-loss:{float(loss_test.item())}")
     best = float(best_loss.item())
     best_model = None
     if best < np.inf:
         best_model = copy.deepcopy(model_glad)
-        with torch.no_grad():
-            off = 0
-            for p in best_model.parameters():
-                p.copy_(best_state[off:off + p.numel()].reshape(p.shape))
-                off += p.numel()
+        best_model.load_packed_(best_state)
     return {"test_loss": best, "model": best_model}
 
 
@@ -423,11 +297,7 @@ def _cv_folds_batched(folds, EPOCHS, lr, INIT_DIAG, L, VERBOSE, sqrt_mode):
         model = None
         if bl[i] < np.inf:
             model = copy.deepcopy(f[3])
-            with torch.no_grad():
-                off = 0
-                for p in model.parameters():
-                    p.copy_(best_P[i, off:off + p.numel()].reshape(p.shape))
-                    off += p.numel()
+            model.load_packed_(best_P[i])
         results[f[0]] = {"test_loss": float(bl[i]), "model": model}
     return results
 
@@ -561,6 +431,44 @@ def get_final_precision_from_batch(predTheta: torch.Tensor, type: str = "min",
     return out.reshape(1, D, D)
 
 
+def _check_shardable(K: int, coll: Collective, what: str) -> None:
+    """Every rank must own at least one matrix: an empty shard would fail locally while the other ranks wait in the first
+    collective.  K and world_size are known everywhere, so every rank raises the same error before any exchange."""
+    if K < coll.world_size:
+        raise ValueError(f"{K} {what} cannot be sharded over {coll.world_size} ranks (need at least one per rank)")
+
+
+def _broadcast_model(model, coll: Collective):
+    """Replicate rank 0's freshly initialised 42 parameters (each rank draws its own otherwise)."""
+    if coll.world_size == 1:
+        return
+    flat = model.packed().detach()
+    if coll.rank != 0:
+        flat.zero_()
+    coll.all_reduce_sum(flat)
+    model.load_packed_(flat)
+
+
+def _train_sharded(Sb, coll: Collective, global_batch: int, EPOCHS, lr, INIT_DIAG, L, VERBOSE, sqrt_mode, loss_Sb=None):
+    """The epoch loop of the missing-data and multi-task modes (ref main.py:600-630, 755-778): ONE model, rank 0's draw, trained on this
+    rank's shard Sb of a batch of `global_batch` matrices; per epoch the pass, the backward, exchange (ii) and the step.  The loss is
+    taken on Sb, or against `loss_Sb`.  Returns (predTheta of the last epoch, model)."""
+    model_glad, optimizer_glad = init_uGLAD(lr=lr, theta_init_offset=1.0, nF=3, H=3)
+    _broadcast_model(model_glad, coll)
+    PRINT_EVERY = _print_every(EPOCHS)
+    predTheta = None
+    for e in range(EPOCHS):
+        optimizer_glad.zero_grad()
+        predTheta, loss = forward_uGLAD(Sb, model_glad, L=L, INIT_DIAG=INIT_DIAG, loss_Sb=loss_Sb, sqrt_mode=sqrt_mode,
+                                        collective=coll, global_batch=global_batch)
+        loss.backward()
+        total = _allreduce_grads(model_glad, loss, coll)
+        optimizer_glad.step()
+        if not e % PRINT_EVERY and VERBOSE:
+            print(f"epoch:{e}/{EPOCHS} loss:{float(total)}")
+    return predTheta, model_glad
+
+
 def run_uGLAD_missing(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, INIT_DIAG=0, L=15, VERBOSE=True,
                       K_batch=3, sqrt_mode=None):
     """Missing-data mode (ref main.py:553-644): mean imputation, K row-subsampled covariances as one multi-task batch whose
@@ -578,19 +486,7 @@ def run_uGLAD_missing(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002,
     S_K = _covariance(X_K, eval_offset)
     if trueTheta is not None:
         trueTheta = _to_dev(trueTheta)
-    model_glad, optimizer_glad = init_uGLAD(lr=lr, theta_init_offset=1.0, nF=3, H=3)
-    _broadcast_model(model_glad, coll)
-    PRINT_EVERY = _print_every(EPOCHS)
-    predTheta = None
-    for e in range(EPOCHS):
-        optimizer_glad.zero_grad()
-        predTheta, loss = forward_uGLAD(S_K, model_glad, L=L, INIT_DIAG=INIT_DIAG, loss_Sb=Sb, sqrt_mode=sqrt_mode,
-                                        collective=coll, global_batch=K_batch)
-        loss.backward()
-        total = _allreduce_grads(model_glad, loss, coll)
-        optimizer_glad.step()
-        if not e % PRINT_EVERY and VERBOSE:
-            print(f"epoch:{e}/{EPOCHS} loss:{float(total)}")
+    predTheta, model_glad = _train_sharded(S_K, coll, K_batch, EPOCHS, lr, INIT_DIAG, L, VERBOSE, sqrt_mode, loss_Sb=Sb)
     predTheta = get_final_precision_from_batch(predTheta, type="min", collective=coll)
     compare_theta = None
     if trueTheta is not None:
@@ -598,29 +494,6 @@ def run_uGLAD_missing(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002,
         if VERBOSE:
             print(f"Comparison - {compare_theta}")
     return predTheta, compare_theta, model_glad
-
-
-def _check_shardable(K: int, coll: Collective, what: str) -> None:
-    """Every rank must own at least one matrix: an empty shard would fail locally while the other ranks wait in the first
-    collective.  K and world_size are known everywhere, so every rank raises the same error before any exchange."""
-    if K < coll.world_size:
-        raise ValueError(f"{K} {what} cannot be sharded over {coll.world_size} ranks (need at least one per rank)")
-
-
-def _broadcast_model(model, coll: Collective):
-    """Replicate rank 0's freshly initialised 42 parameters (each rank draws its own otherwise)."""
-    if coll.world_size == 1:
-        return
-    with torch.no_grad():
-        flat = torch.cat([p.reshape(-1) for p in model.parameters()])
-        if coll.rank != 0:
-            flat.zero_()
-        coll.all_reduce_sum(flat)
-        off = 0
-        for p in model.parameters():
-            n = p.numel()
-            p.copy_(flat[off:off + n].reshape(p.shape))
-            off += n
 
 
 def run_uGLAD_multitask(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.002, INIT_DIAG=0, L=15, VERBOSE=True,
@@ -633,19 +506,7 @@ def run_uGLAD_multitask(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.00
     _check_shardable(K, coll, "tasks")
     lo, hi = coll.shard(K)
     Sb = _covariance(Xb[lo:hi], eval_offset)
-    model_glad, optimizer_glad = init_uGLAD(lr=lr, theta_init_offset=1.0, nF=3, H=3)
-    _broadcast_model(model_glad, coll)
-    PRINT_EVERY = _print_every(EPOCHS)
-    predTheta = None
-    for e in range(EPOCHS):
-        optimizer_glad.zero_grad()
-        predTheta, loss = forward_uGLAD(Sb, model_glad, L=L, INIT_DIAG=INIT_DIAG, sqrt_mode=sqrt_mode, collective=coll,
-                                        global_batch=K)
-        loss.backward()
-        total = _allreduce_grads(model_glad, loss, coll)
-        optimizer_glad.step()
-        if not e % PRINT_EVERY and VERBOSE:
-            print(f"epoch:{e}/{EPOCHS} loss:{float(total)}")
+    predTheta, model_glad = _train_sharded(Sb, coll, K, EPOCHS, lr, INIT_DIAG, L, VERBOSE, sqrt_mode)
     predTheta = coll.all_gather_cat(predTheta.detach())
     compare_theta = []
     if trueTheta is not None:
@@ -657,9 +518,8 @@ def run_uGLAD_multitask(Xb, trueTheta=None, eval_offset=0.1, EPOCHS=250, lr=0.00
 
 
 # ============================================================================================ public classes
-class uGLAD_GL(object):
-    """Drop-in for the reference's `uGLAD_GL` (main.py:34-151): `fit` sets covariance_ (float64), precision_ (float32),
-    location_, node_names_, model_glad and returns the metrics dict (or None) -- not self, like the reference."""
+class _Estimator(object):
+    """What the two estimators share: their attributes, the end of a fit, the no_grad pass behind predict(), recovered_graph()."""
 
     def __init__(self, device_covariance: bool = False):
         """device_covariance (additive): form the input covariances + eigenvalue repair on the GPU."""
@@ -667,11 +527,51 @@ class uGLAD_GL(object):
         self.device_covariance = bool(device_covariance)
         self.covariance_: Optional[np.ndarray] = None
         self.precision_: Optional[np.ndarray] = None
-        self.location_: Optional[np.ndarray] = None
-        self.data_min_: Optional[np.ndarray] = None    # (additive) column minima and ranges of the table fit() normalised: what
+        self.location_: Optional[np.ndarray] = None    # (uGLAD_multitask: (K, D), the tasks' means)
+        self.data_min_: Optional[np.ndarray] = None    # (additive) column minima and ranges of the table(s) fit() normalised: what
         self.data_range_: Optional[np.ndarray] = None  # places a new row in the model's coordinates (mahalanobis, score_samples, score)
         self.model_glad: Optional[GladParams] = None
         self._fit_cfg = None
+
+    def _finish_fit(self, start, verbose, precision, model_glad, cond_max, compare_theta, **cfg):
+        """The end of every fit: precision_ (a device tensor or None), model_glad, what predict() needs of the fit's arguments (`cfg`),
+        cond_max_ -- the regime diagnostic (additive): the largest cond(b^T b + 4/lambda I) any pass of this fit saw, from
+        warn_if_outside, which the caller runs so that the warning points at the caller's caller -- and the runtime line."""
+        if precision is not None:
+            self.precision_ = precision.detach().cpu().numpy()
+        if model_glad is not None:
+            self.model_glad = model_glad
+        self._fit_cfg = cfg
+        self.cond_max_ = cond_max
+        if verbose:
+            print(f"Total runtime: {time() - start} secs\n")
+        return compare_theta
+
+    def _forward(self, tables, S):
+        """The no_grad pass behind predict(): the trained model over the covariances S ((D, D) or (K, D, D)), or over those of the
+        `tables`, processed like fit() processes its own -> (Theta (K, D, D) as a numpy array, the pass's regime monitor)."""
+        if self.model_glad is None:
+            raise ValueError("call fit() first")
+        cfg = self._fit_cfg
+        if S is None:
+            tables = [np.array(prepare_data.process_table(X, NORM="min_max", VERBOSE=False)) for X in tables]
+            S = prepare_data.get_covariance(tables, offset=cfg["eval_offset"])
+        S = np.asarray(S, dtype=np.float64)
+        with torch.no_grad(), glad.regime_monitor() as regime:
+            theta = glad.glad(_to_dev(S[None] if S.ndim == 2 else S), self.model_glad, L=cfg["L"], INIT_DIAG=cfg["INIT_DIAG"],
+                              sqrt_mode=cfg["sqrt_mode"], collective=Collective())
+        return theta.cpu().numpy(), regime
+
+    def recovered_graph(self, sparsity: float = 0.1):
+        """The graph(s) of the fitted precision_ (recovered_graph): the `sparsity` fraction of the edges with the largest |rho|."""
+        if self.precision_ is None:
+            raise ValueError("call fit() first")
+        return recovered_graph(self.precision_, sparsity=sparsity)
+
+
+class uGLAD_GL(_Estimator):
+    """Drop-in for the reference's `uGLAD_GL` (main.py:34-151): `fit` sets covariance_ (float64), precision_ (float32),
+    location_, node_names_, model_glad and returns the metrics dict (or None) -- not self, like the reference."""
 
     def fit(self, X, true_theta=None, eval_offset=0.1, centered=False, epochs=250, lr=0.002, INIT_DIAG=0, L=15,
             verbose=True, k_fold=3, mode="direct", node_names=None, sqrt_mode=None, parallel_folds=False,
@@ -701,16 +601,21 @@ class uGLAD_GL(object):
         self.location_ = X.mean(axis=0)
         self.data_min_, self.data_range_ = data_min, data_range
         self.node_names_ = list(node_names) if node_names is not None else [f"node_{i}" for i in range(D)]
-        if pred_theta is not None:
-            self.precision_ = pred_theta[0].detach().cpu().numpy()
-        if model_glad is not None:
-            self.model_glad = model_glad
-        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
-        # regime diagnostic (additive): the largest cond(b^T b + 4/lambda I) any pass of this fit saw; warns beyond the validated bound
-        self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit", get_collective() if mode == "missing" else None)  # (the sharded mode)
-        if verbose:
-            print(f"Total runtime: {time() - start} secs\n")
-        return compare_theta
+        cond_max = regime.warn_if_outside("uGLAD_GL.fit", get_collective() if mode == "missing" else None)  # (the sharded mode)
+        return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+
+    @staticmethod
+    def _train_direct_on(A, true_theta, eval_offset, epochs, lr, INIT_DIAG, L, verbose, sqrt_mode):
+        """Direct-mode training on the (1, D, D) device matrix A that takes the covariance's place (fit_mixed, fit_copula):
+        run_uGLAD_direct's three results and the regime monitor of its passes."""
+        D = A.shape[-1]
+        true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
+        with glad.regime_monitor() as regime:
+            pred_theta, compare_theta, model_glad = run_uGLAD_direct(None, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs,
+                                                                     lr=lr, INIT_DIAG=INIT_DIAG, L=L, VERBOSE=verbose,
+                                                                     sqrt_mode=sqrt_mode, Sb=A)
+        return pred_theta, compare_theta, model_glad, regime
 
     def fit_mixed(self, df, dtype, true_theta=None, eval_offset=0.1, epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True,
                   sqrt_mode=None):
@@ -726,28 +631,18 @@ class uGLAD_GL(object):
         if verbose:
             print("Running uGLAD on a mixed table")
         table, maps = prepare_data.encode_mixed_table(df, dtype)
-        D = table.shape[1]
         A, mn, A64 = _lib.get_lib().association(torch.from_numpy(table[None]).to(_lib.device()), maps, eval_offset=eval_offset,
                                                 repair=True, want_f64=True)
-        true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
-        with glad.regime_monitor() as regime:
-            pred_theta, compare_theta, model_glad = run_uGLAD_direct(None, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs,
-                                                                     lr=lr, INIT_DIAG=INIT_DIAG, L=L, VERBOSE=verbose,
-                                                                     sqrt_mode=sqrt_mode, Sb=A)
+        pred_theta, compare_theta, model_glad, regime = self._train_direct_on(A, true_theta, eval_offset, epochs, lr, INIT_DIAG, L,
+                                                                              verbose, sqrt_mode)
         self.covariance_ = A64[0].cpu().numpy()
         self.association_min_eig_ = float(mn[0])
         self.location_ = np.where(maps.kinds == "r", table.mean(axis=0), np.nan)
         self.data_min_ = self.data_range_ = None  # (a mixed table is not normalised, and its rows cannot be scored)
         self.node_names_ = [str(n) for n in maps.names]
-        if pred_theta is not None:
-            self.precision_ = pred_theta[0].detach().cpu().numpy()
-        if model_glad is not None:
-            self.model_glad = model_glad
-        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
-        self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit_mixed", None)
-        if verbose:
-            print(f"Total runtime: {time() - start} secs\n")
-        return compare_theta
+        cond_max = regime.warn_if_outside("uGLAD_GL.fit_mixed", None)
+        return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
 
     def fit_copula(self, X, method="kendall", true_theta=None, eval_offset=0.1, epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True,
                    sqrt_mode=None):
@@ -771,52 +666,24 @@ class uGLAD_GL(object):
         constant = np.nonzero(out.info[0].cpu().numpy() & 2)[0]
         if len(constant):
             raise ValueError(f"fit_copula: constant columns have no rank correlation: {[names[i] for i in constant]}")
-        true_theta_b = None if true_theta is None else np.asarray(true_theta).reshape(1, D, D)
-        with glad.regime_monitor() as regime:
-            pred_theta, compare_theta, model_glad = run_uGLAD_direct(None, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs,
-                                                                     lr=lr, INIT_DIAG=INIT_DIAG, L=L, VERBOSE=verbose,
-                                                                     sqrt_mode=sqrt_mode, Sb=out.A)
+        pred_theta, compare_theta, model_glad, regime = self._train_direct_on(out.A, true_theta, eval_offset, epochs, lr, INIT_DIAG, L,
+                                                                              verbose, sqrt_mode)
         self.covariance_ = out.A64[0].cpu().numpy()
         self.copula_min_eig_ = float(out.min_eig[0])
         self.location_ = tables[0].mean(axis=0)
         self.data_min_ = self.data_range_ = None  # (rows of a copula fit are not scored)
         self.node_names_ = names
-        if pred_theta is not None:
-            self.precision_ = pred_theta[0].detach().cpu().numpy()
-        if model_glad is not None:
-            self.model_glad = model_glad
-        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
-        self.cond_max_ = regime.warn_if_outside("uGLAD_GL.fit_copula", None)
-        if verbose:
-            print(f"Total runtime: {time() - start} secs\n")
-        return compare_theta
-
-    def recovered_graph(self, sparsity: float = 0.1):
-        """The graph of the fitted precision_ (recovered_graph): the `sparsity` fraction of the edges with the largest |rho|."""
-        if self.precision_ is None:
-            raise ValueError("call fit() first")
-        return recovered_graph(self.precision_, sparsity=sparsity)
+        cond_max = regime.warn_if_outside("uGLAD_GL.fit_copula", None)
+        return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
 
     def predict(self, X=None, S=None) -> np.ndarray:
         """Inference-only pass: the trained 42 parameters applied to new data (no_grad forward, the reference's
         main.py:539-540 pattern).  Give a samples table X (processed like `fit` does) or covariance(s) S.
         Warns (UgladRegimeWarning) when the pass leaves the validated regime -- e.g. an un-normalised covariance given as S."""
-        if self.model_glad is None:
-            raise ValueError("call fit() first")
-        cfg = self._fit_cfg
-        if S is None:
-            X = np.array(prepare_data.process_table(X, NORM="min_max", VERBOSE=False))
-            S = prepare_data.get_covariance(X[None], offset=cfg["eval_offset"])
-        S = np.asarray(S, dtype=np.float64)
-        if S.ndim == 2:
-            S = S[None]
-        with torch.no_grad(), glad.regime_monitor() as regime:
-            theta = glad.glad(_to_dev(S), self.model_glad, L=cfg["L"], INIT_DIAG=cfg["INIT_DIAG"],
-                              sqrt_mode=cfg["sqrt_mode"], collective=Collective())
+        out, regime = self._forward([X], S)
         self.predict_cond_max_ = regime.warn_if_outside("uGLAD_GL.predict")
-        out = theta.cpu().numpy()
         return out[0] if out.shape[0] == 1 else out
-
 
     # ---- scoring rows (additive: sklearn's covariance estimators carry these three, the reference none)
     def _model_coordinates(self, X, normalized: bool) -> np.ndarray:
@@ -842,19 +709,12 @@ class uGLAD_GL(object):
         return float(np.mean(self.score_samples(X, normalized=normalized)))
 
 
-class uGLAD_multitask(object):
+class uGLAD_multitask(_Estimator):
     """Drop-in for the reference's `uGLAD_multitask` (main.py:155-226): K tables, one shared model, batched attributes."""
 
     def __init__(self, device_covariance: bool = False):
-        super().__init__()
-        self.device_covariance = bool(device_covariance)
-        self.covariance_ = []
-        self.precision_: Optional[np.ndarray] = None
-        self.location_: Optional[np.ndarray] = None    # (additive) (K, D) each: the tasks' means, and the column minima and ranges of
-        self.data_min_: Optional[np.ndarray] = None    # the tables fit() normalised (mahalanobis, score_samples, score)
-        self.data_range_: Optional[np.ndarray] = None
-        self.model_glad: Optional[GladParams] = None
-        self._fit_cfg = None
+        super().__init__(device_covariance)
+        self.covariance_ = []  # (load_uGLAD_model tells the two classes apart by this)
 
     def fit(self, Xb, true_theta_b=None, eval_offset=0.1, centered=False, epochs=250, lr=0.002, INIT_DIAG=0, L=15,
             verbose=True, sqrt_mode=None):
@@ -869,35 +729,17 @@ class uGLAD_multitask(object):
                 Xb, trueTheta=true_theta_b, eval_offset=eval_offset, EPOCHS=epochs, lr=lr, INIT_DIAG=INIT_DIAG, L=L,
                 VERBOSE=verbose, sqrt_mode=sqrt_mode)
         self.covariance_ = np.array([prepare_data.empirical_covariance(X, assume_centered=centered) for X in Xb])
-        self.precision_ = pred_theta.detach().cpu().numpy()
         self.location_ = np.array([X.mean(axis=0) for X in Xb])
         self.data_min_, self.data_range_ = np.array([m for m, _ in min_range]), np.array([r for _, r in min_range])
-        self.model_glad = model_glad
-        self._fit_cfg = dict(L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
-        self.cond_max_ = regime.warn_if_outside("uGLAD_multitask.fit", get_collective())
-        if verbose:
-            print(f"Total runtime: {time() - start} secs\n")
-        return compare_theta
-
-    def recovered_graph(self, sparsity: float = 0.1):
-        """The K graphs of the fitted precision_ (recovered_graph): the `sparsity` fraction of the edges with the largest |rho|."""
-        if self.precision_ is None:
-            raise ValueError("call fit() first")
-        return recovered_graph(self.precision_, sparsity=sparsity)
+        cond_max = regime.warn_if_outside("uGLAD_multitask.fit", get_collective())
+        return self._finish_fit(start, verbose, pred_theta, model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
 
     def predict(self, Xb=None, S=None) -> np.ndarray:
         """no_grad forward of the trained model on new tables (list) or covariances (K, D, D)."""
-        if self.model_glad is None:
-            raise ValueError("call fit() first")
-        cfg = self._fit_cfg
-        if S is None:
-            Xb = [np.array(prepare_data.process_table(X, NORM="min_max", VERBOSE=False)) for X in Xb]
-            S = prepare_data.get_covariance(Xb, offset=cfg["eval_offset"])
-        with torch.no_grad(), glad.regime_monitor() as regime:
-            theta = glad.glad(_to_dev(np.asarray(S, dtype=np.float64)), self.model_glad, L=cfg["L"],
-                              INIT_DIAG=cfg["INIT_DIAG"], sqrt_mode=cfg["sqrt_mode"], collective=Collective())
+        out, regime = self._forward(Xb, S)
         self.predict_cond_max_ = regime.warn_if_outside("uGLAD_multitask.predict")
-        return theta.cpu().numpy()
+        return out
 
 
     # ---- scoring rows (additive, as uGLAD_GL's)
@@ -929,413 +771,6 @@ class uGLAD_multitask(object):
         return np.array([float(np.mean(d)) for d in self._scores(X, normalized).log_density])
 
 
-# ============================================================================================ scoring rows against fitted models
-class SampleScores(NamedTuple):
-    """What sample_scores returns, float64 numpy arrays."""
-    mahalanobis: np.ndarray   # (K, N) squared distances xc^T P xc ((N,) for a single (D, D) model)
-    log_density: np.ndarray   # (K, N) (logdet P - D log 2 pi - q) / 2
-    logdet: np.ndarray        # (K,)   (a float64 scalar for a single model); NaN where P is not positive definite
-
-
-SCORE_ROW_CHUNK = 65536  # rows per call of uglad_sample_scores unless row_chunk says otherwise (halved while the workspace is refused)
-
-
-def _to_model_coordinates(X, min_range, D: int) -> np.ndarray:
-    """(N, D) float64: X as given (min_range None) or mapped by (X - min) / range, the normalisation fit() applied to its own table."""
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim != 2 or X.shape[1] != D:
-        raise ValueError(f"X must be (N, {D}): the columns fit() kept, in node_names_ order; got {X.shape}")
-    if min_range is None:
-        return X
-    mn, rg = min_range
-    if mn is None or rg is None:
-        raise ValueError("this model carries no data_min_ / data_range_ (fitted before they were kept?): pass normalized=True")
-    return (X - mn) / rg
-
-
-def sample_scores(precision, location, X, row_chunk=None) -> SampleScores:
-    """Squared Mahalanobis distance and Gaussian log-density of every row of X under every model, on the device in fp64
-    (uglad_sample_scores, csrc/score_wide.h): precision (D, D) or (K, D, D) -- its symmetric part is used --, location (D,) or (K, D), X
-    (N, D) (one table for every model) or (K, N, D); numpy arrays or device tensors.  Rows go through in chunks of `row_chunk` (default
-    SCORE_ROW_CHUNK, less where the workspace demands it), so any N fits; a row's numbers do not depend on the chunking, bit for bit.  A
-    model that is not positive definite gets NaN in logdet and log_density and keeps its distances; a NaN in a row stays in that row."""
-    lib = _lib.get_lib()
-    dev = _lib.device()
-
-    def to(a):
-        if torch.is_tensor(a):
-            return a.detach().to(device=dev, dtype=torch.float64).contiguous()
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-
-    single = np.ndim(precision) == 2
-    if np.ndim(precision) not in (2, 3) or np.shape(precision)[-1] > lib.max_dim:
-        raise ValueError(f"precision must be (D, D) or (K, D, D) with D <= max_dim = {lib.max_dim}; got {tuple(np.shape(precision))}")
-    P, mu = to(precision), to(location)
-    P = P[None] if P.dim() == 2 else P
-    mu = mu[None] if mu.dim() == 1 else mu
-    if P.dim() != 3 or P.shape[1] != P.shape[2] or tuple(mu.shape) != tuple(P.shape[:2]):
-        raise ValueError(f"precision (K, D, D) and location (K, D); got {tuple(P.shape)} and {tuple(mu.shape)}")
-    K, D = mu.shape
-    if not torch.is_tensor(X):
-        X = np.asarray(X, dtype=np.float64)
-    X = X[None] if X.ndim == 2 else X
-    if X.ndim != 3 or X.shape[2] != D or X.shape[0] not in (1, K) or X.shape[1] < 1:
-        raise ValueError(f"X must be (N, {D}) or ({K}, N, {D}) with N >= 1; got {tuple(X.shape)}")
-    N = X.shape[1]
-    chunk = min(N, int(row_chunk) if row_chunk else SCORE_ROW_CHUNK)
-    if chunk < 1:
-        raise ValueError("row_chunk must be positive")
-    while chunk > 1 and int(lib._dll.uglad_sample_scores_workspace_floats(K, chunk, D)) < 0:
-        chunk = (chunk + 1) // 2
-    maha, dens, logdet = np.empty((K, N)), np.empty((K, N)), None
-    for a in range(0, N, chunk):
-        q, ld, det = lib.sample_scores(to(X[:, a:a + chunk]), P, mu)
-        maha[:, a:a + chunk], dens[:, a:a + chunk] = q.cpu().numpy(), ld.cpu().numpy()
-        logdet = det.cpu().numpy() if logdet is None else logdet  # (the same bits in every chunk)
-    if single:
-        return SampleScores(maha[0], dens[0], logdet[0])
-    return SampleScores(maha, dens, logdet)
-
-
-# ============================================================================================ after the path (SURVEY 8f N3, N4)
-METRIC_KEYS = ("FDR", "TPR", "FPR", "SHD", "nnzTrue", "nnzPred", "precision", "recall", "Fbeta", "aupr", "auc")
-
-
-# Smallest D > max_eig_dim whose metrics report goes to uglad_support_metrics_wide; below it (and above max_eig_dim) the host formulation
-# would run.  0: the whole range goes to the device.  scripts/metrics_wide_probe.py times both sides; a range where the host wins end to
-# end belongs here.
-WIDE_METRICS_MIN_DIM = 0
-
-
-def device_report_metrics(true_theta, pred_theta, beta: int = 1):
-    """`report_metrics_all` (ref utils/metrics.py:25-108) for K (true, predicted) precision matrices at once, counted on the
-    device: list of K dicts with the reference's keys, rounded to 3 decimals as the reference does.  D <= max_eig_dim:
-    uglad_support_metrics (one workgroup per pair); beyond, up to max_dim: uglad_support_metrics_wide (the edges sorted by score, many
-    workgroups per pair)."""
-    lib = _lib.get_lib()
-    dev = _lib.device()
-    T = torch.as_tensor(np.asarray(true_theta.detach().cpu() if torch.is_tensor(true_theta) else true_theta).real,
-                        dtype=torch.float32) if not (torch.is_tensor(true_theta) and true_theta.device == dev) else true_theta
-    G = pred_theta if torch.is_tensor(pred_theta) else torch.as_tensor(np.asarray(pred_theta).real, dtype=torch.float32)
-    T = T.detach().to(device=dev, dtype=torch.float32)
-    G = G.detach().to(device=dev, dtype=torch.float32)
-    if T.dim() == 2:
-        T, G = T[None], G[None]
-    D = T.shape[-1]
-    if D > lib.max_dim or lib.max_eig_dim < D < WIDE_METRICS_MIN_DIM:
-        # beyond what the device covers: the report is evaluated where the reference evaluates it -- on the host, from the same definitions
-        # (utils/metrics.py = ref utils/metrics.py:25-108).  After the path, once per fit; round 3 raised UgladError here AFTER all epochs
-        # of a fit(X, true_theta=...) at D > 256 had run.
-        Tn, Gn = T.cpu().numpy(), G.cpu().numpy()
-        return [report_metrics_all(Tn[k], Gn[k], beta=beta) for k in range(Tn.shape[0])]
-    metrics = lib.support_metrics if D <= lib.max_eig_dim else lib.support_metrics_wide
-    out = metrics(T.contiguous(), G.contiguous(), beta=beta).cpu().numpy()
-    return [{k: round(float(v), 3) for k, v in zip(METRIC_KEYS, row)} for row in out]
-
-
-def get_partial_correlations(precision):
-    """rho_ij = -p_ij / sqrt(p_ii p_jj), ones on the diagonal (ref main.py:796-821: its double loop fills the upper triangle
-    with that formula and mirrors it).  (D,D) or (K,D,D).
-    A host array (what the reference takes: `precision_` is numpy) is evaluated on the host in float64 like the reference -- an O(D^2)
-    formula needs no GPU and loses nothing to fp32; a tensor already on the device goes through uglad_partial_correlations (fp32, K
-    matrices per launch) and comes back as a device tensor."""
-    if torch.is_tensor(precision) and precision.is_cuda:
-        P = precision.detach().to(dtype=torch.float32)
-        single = P.dim() == 2
-        rho = _lib.get_lib().partial_correlations((P[None] if single else P).contiguous())
-        return rho[0] if single else rho
-    P = np.asarray(precision.detach().cpu() if torch.is_tensor(precision) else precision, dtype=np.float64)
-    d = np.sqrt(np.diagonal(P, axis1=-2, axis2=-1))
-    up = np.triu(-P / (d[..., :, None] * d[..., None, :]), k=1)  # the reference reads the upper triangle and mirrors it
-    rho = up + np.swapaxes(up, -1, -2)
-    idx = np.arange(P.shape[-1])
-    rho[..., idx, idx] = 1.0
-    return rho
-
-
-# -------------------------------------------------------------------------------------------- the recovered graph
-GRAPH_STAT_KEYS = ("num_nodes", "num_edges", "avg_degree", "density", "avg_clustering", "transitivity", "diameter", "avg_shortest_path")
-
-
-class RecoveredGraph(object):
-    """One recovered graph: `edges` (m, 2) int32 with i < j in row-major order, `weights` (m,) -- the partial correlation of every edge
-    (float32 from the device, float64 from the host formulation) -- `threshold`, `degree` (D,), `triangles` (D,) (None without stats) and
-    `stats`, a dict with the keys of the reference's compute_graph_statistics (diameter and avg_shortest_path None: networkx's to give)."""
-
-    __slots__ = ("edges", "weights", "threshold", "degree", "triangles", "stats")
-
-    def __init__(self, edges, weights, threshold, degree, triangles, stats):
-        self.edges, self.weights, self.threshold, self.degree, self.triangles, self.stats = edges, weights, threshold, degree, triangles, stats
-
-    @property
-    def positive(self) -> np.ndarray:
-        """(m,) bool: the edge's sign ("+", the reference's green: rho > th)."""
-        return self.weights > self.threshold
-
-
-def _stats_dict(six) -> dict:
-    d = {"num_nodes": int(six[0]), "num_edges": int(six[1])}
-    d.update({key: float(x) for key, x in zip(GRAPH_STAT_KEYS[2:6], six[2:6])})
-    d["diameter"] = d["avg_shortest_path"] = None
-    return d
-
-
-def _n_keep(sparsity, D: int) -> int:
-    E = D * (D - 1) // 2
-    n = int(sparsity * E)  # (ref main.py:865)
-    if not 0 <= n <= E:
-        raise ValueError(f"sparsity {sparsity} keeps {n} of {E} edges")
-    return n
-
-
-def _recovered_graph_host(values, from_precision: bool, n_keep, threshold, stats: bool) -> RecoveredGraph:
-    """uglad_graph_wide's definitions for ONE (D, D) matrix on the host in float64, vectorised (sort, compare, (A A) o A): for a host array
-    whose values float32 cannot hold -- rounding could merge a value with the threshold -- and for sizes the device does not cover."""
-    V = np.asarray(values, dtype=np.float64)
-    D = V.shape[-1]
-    i, j = np.triu_indices(D, 1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rho = -V[i, j] / np.sqrt(V[i, i] * V[j, j]) if from_precision else V[i, j]
-    if n_keep is None:
-        th = np.float64(threshold)
-    else:
-        s = np.sort(np.abs(rho))
-        th = s[len(s) - n_keep] if n_keep > 0 else s[0]  # (the reference's rho_upper[-0])
-    keep = (rho > th) | (rho < -th)
-    ei, ej = i[keep], j[keep]
-    A = np.zeros((D, D))
-    A[ei, ej] = A[ej, ei] = 1.0
-    degree = A.sum(axis=1).astype(np.int64)
-    triangles = st = None
-    if stats:
-        t2 = ((A @ A) * A).sum(axis=1).astype(np.int64)  # (exact: integers below 2^53)
-        triangles = t2 // 2
-        st = _stats_dict(_six_statistics(D, int(keep.sum()), degree, t2))
-    return RecoveredGraph(np.stack([ei, ej], axis=1).astype(np.int32), rho[keep], th, degree, triangles, st)
-
-
-def _six_statistics(D: int, m: int, degree, t2):
-    """The operations networkx performs (density, average_clustering, transitivity), in its order, on Python integers."""
-    d = [int(x) for x in degree]
-    t = [int(x) for x in t2]
-    c = [0 if ti == 0 else ti / (di * (di - 1)) for di, ti in zip(d, t)]
-    return (D, m, sum(d) / D, m / (D * (D - 1)) * 2, sum(c) / D, 0 if sum(t) == 0 else sum(t) / sum(di * (di - 1) for di in d))
-
-
-def _fits_float32(a: np.ndarray) -> bool:
-    if a.dtype == np.float32:
-        return True
-    with np.errstate(over="ignore", invalid="ignore"):
-        back = a.astype(np.float32).astype(a.dtype)
-    return bool(np.all((back == a) | (a != a)))
-
-
-def _recovered_graphs(values, from_precision: bool, n_keep, threshold, stats: bool):
-    """K graphs of a (K, D, D) device tensor or host array: on the device wherever float32 holds the values (uglad_graph_wide), else by
-    the host formulation."""
-    lib = _lib.get_lib()
-    on_device = torch.is_tensor(values) and values.device.type != "cpu"
-    host = None if on_device else np.asarray(values.detach() if torch.is_tensor(values) else values)
-    K, D = int(values.shape[0]), int(values.shape[-1])
-    if D < 2 or D > lib.max_dim or not (on_device or _fits_float32(host)):
-        host = values.detach().cpu().numpy() if on_device else host
-        return [_recovered_graph_host(host[k], from_precision, n_keep, threshold, stats) for k in range(K)]
-    V = values.detach() if on_device else torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32))
-    V = V.to(device=_lib.device(), dtype=torch.float32).contiguous()
-    g = lib.graph_wide(V, n_keep=n_keep, threshold=None if n_keep is not None else threshold, from_precision=from_precision, want_stats=stats)
-    count = g.edge_count.cpu().numpy()
-    th, degree = g.threshold.cpu().numpy(), g.degree.cpu().numpy()
-    t2, six = (g.triangles2.cpu().numpy(), g.stats.cpu().numpy()) if stats else (None, None)
-    out = []
-    for k in range(K):
-        m = int(count[k])
-        out.append(RecoveredGraph(g.edge_ij[k, :m].cpu().numpy(), g.edge_w[k, :m].cpu().numpy(), th[k], degree[k],
-                                  t2[k] // 2 if stats else None, _stats_dict(six[k]) if stats else None))
-    return out
-
-
-def recovered_graph(precision, sparsity: float = 0.1, threshold=None, stats: bool = True):
-    """The graph a precision matrix stands for (ref main.py:985-1005: partial correlations, then the `sparsity` fraction of the edges
-    with the largest |rho|; or every edge beyond a given `threshold`), with degrees, triangle counts and the statistics of the reference's
-    compute_graph_statistics, all computed on the device (uglad_graph_wide).  (D, D) or (K, D, D), a numpy array or a device tensor ->
-    a RecoveredGraph or a list of K.  No networkx: graph_from_partial_correlations builds its nx.Graph from the same edge list."""
-    single = len(precision.shape) == 2
-    P = precision[None] if single else precision
-    n_keep = None if threshold is not None else _n_keep(sparsity, int(P.shape[-1]))
-    out = _recovered_graphs(P, True, n_keep, threshold, stats)
-    return out[0] if single else out
-
-
-def graph_from_partial_correlations(rho, names, sparsity=1, title="", fig_size=12, PLOT=True, save_file=None, roundOFF=5):
-    """The reference's graph_from_partial_correlations (main.py:825-946), same arguments and return values: (nx.Graph with every node
-    of `names` and the kept edges -- attributes color, weight rounded to `roundOFF` decimals, label -- , the PNG bytes of its drawing or
-    None without PLOT, the edge list as strings).  The threshold, the membership test and the edge order come from uglad_graph_wide instead
-    of a Python loop over D^2 entries: a device tensor stays on the device, a host array goes there when float32 holds its values
-    exactly, and is otherwise evaluated on the host in float64 (rounding could merge values with the threshold)."""
-    import networkx as nx
-
-    names = list(names)
-    D = int(rho.shape[-1])
-    g = _recovered_graphs(rho[None], False, _n_keep(sparsity, D), None, False)[0]
-    G = nx.Graph()
-    G.add_nodes_from(names)
-    edge_strings = []
-    for (i, j), w, plus in zip(g.edges.tolist(), g.weights, g.positive):
-        colour, w = ("green", "+") if plus else ("red", "-"), round(np.float64(w), roundOFF)
-        G.add_edge(names[i], names[j], color=colour[0], weight=w, label=colour[1])
-        edge_strings.append(f"({names[i]}, {names[j]}, {w}, {colour[0]})")
-    return G, _draw_graph(G, title, fig_size, save_file) if PLOT else None, edge_strings
-
-
-def _draw_graph(G, title, fig_size, save_file):
-    """PNG bytes of a spring layout of G: grey nodes with their names just above them, edges in their colour, as wide as |weight| relative
-    to the largest."""
-    import io
-
-    import matplotlib.pyplot as plt
-    import networkx as nx
-
-    colours = [c for _, _, c in G.edges(data="color")]
-    widths = np.abs(np.array([w for _, _, w in G.edges(data="weight")], dtype=np.float64))
-    if widths.size:
-        widths = widths / widths.max()
-    fig = plt.figure(figsize=(fig_size, fig_size))
-    try:
-        ax = fig.gca()
-        where = nx.spring_layout(G, scale=0.2, k=1.0 / np.sqrt(G.number_of_edges() + 10))
-        nx.draw_networkx_nodes(G, where, node_color="grey", node_size=100, ax=ax)
-        nx.draw_networkx_edges(G, where, edge_color=colours, width=widths, ax=ax)
-        nx.draw_networkx_labels(G, {node: (x, y + 0.008) for node, (x, y) in where.items()}, ax=ax)
-        ax.set_title(str(title), fontsize=20)
-        ax.margins(0.15)
-        fig.tight_layout()
-        if save_file:
-            fig.savefig(save_file, bbox_inches="tight")
-        png = io.BytesIO()
-        fig.savefig(png)
-        return png.getvalue()
-    finally:
-        plt.close(fig)
-
-
-def compute_graph_statistics(G):
-    """The reference's compute_graph_statistics (main.py:1263-1300): a one-row DataFrame with num_nodes, num_edges, avg_degree, density,
-    avg_clustering, transitivity, diameter, avg_shortest_path.  The first six are counted on the device from G's adjacency matrix
-    (uglad_graph_wide with the threshold 0.5: degrees, the triangle product); the last two are all-pairs searches and stay networkx's,
-    for a connected graph only.  A graph the device does not cover (fewer than 2 or more than max_dim nodes, self-loops, directed or
-    parallel edges) is networkx's as a whole."""
-    import networkx as nx
-    import pandas as pd
-
-    D = G.number_of_nodes()
-    if D < 2 or D > _lib.get_lib().max_dim or G.is_directed() or G.is_multigraph() or nx.number_of_selfloops(G):
-        row = {"num_nodes": D, "num_edges": G.number_of_edges(), "avg_degree": sum(dict(G.degree()).values()) / D if D > 0 else 0,
-               "density": nx.density(G), "avg_clustering": nx.average_clustering(G), "transitivity": nx.transitivity(G)}
-    else:
-        A = nx.to_numpy_array(G, dtype=np.float32, weight=None)
-        row = _recovered_graphs(A[None], False, None, 0.5, True)[0].stats
-    connected = nx.is_connected(G)
-    row["diameter"] = nx.diameter(G) if connected else None
-    row["avg_shortest_path"] = nx.average_shortest_path_length(G) if connected else None
-    return pd.DataFrame([{key: row[key] for key in GRAPH_STAT_KEYS}])
-
-
-# Smallest D > max_eig_dim that goes to uglad_conditional_mean_wide; below it (and above max_eig_dim) the host formulation would run.  0: the
-# whole range goes to the device.  scripts/after_wide_probe.py times both sides; a range where the host wins end to end belongs here.
-WIDE_CONDITIONAL_MIN_DIM = 0
-
-
-def conditional_gaussian_batch(precision, mean, observed_mask, observed_values, clip01: bool = False, want_cov: bool = True):
-    """K conditional-Gaussian problems on the device: precision (K,D,D), mean (K,D), observed_mask (K,D) bool, observed_values (K,D)
-    (read where observed) -> full_mean (K,D), cond_cov (K,D,D) (L_uu^-1 on the unobserved block, identity elsewhere), log_pdf (K) --
-    fp32 torch tensors on the device.  D <= max_eig_dim: uglad_conditional_mean (the path's eigensolver, fp32); beyond, up to max_dim:
-    uglad_conditional_mean_wide (fp64 Cholesky, many workgroups per problem; `want_cov=False` skips the inverse and returns None for it)."""
-    full, cov, logp = _conditional_gaussian_device(precision, mean, observed_mask, observed_values, clip01, want_cov)
-    return full.to(torch.float32), cov, logp.to(torch.float32)
-
-
-def _conditional_gaussian_device(precision, mean, observed_mask, observed_values, clip01, want_cov):
-    """conditional_gaussian_batch in the precision the entry point computes in: full_mean and log_pdf are fp64 beyond max_eig_dim."""
-    dev = _lib.device()
-    lib = _lib.get_lib()
-
-    def to(a, dtype):
-        # a host array is converted on the host and uploaded once; a device tensor is converted on the device
-        if torch.is_tensor(a):
-            return a.detach().to(device=dev, dtype=dtype).contiguous()
-        return torch.as_tensor(np.asarray(a), dtype=dtype).to(dev).contiguous()
-
-    D = np.shape(precision)[-1]
-    if D <= lib.max_eig_dim:
-        f = lambda a: to(a, torch.float32)  # noqa: E731
-        return lib.conditional_mean(f(precision), f(mean), f(observed_mask), f(observed_values), clip01=clip01)
-    if D > lib.max_dim or D < WIDE_CONDITIONAL_MIN_DIM:
-        return _conditional_gaussian_host(precision, mean, observed_mask, observed_values, clip01, dev)
-    f = lambda a: to(a, torch.float64)  # noqa: E731
-    return lib.conditional_mean_wide(f(precision), f(mean), to(observed_mask, torch.float32), f(observed_values), clip01=clip01,
-                                     want_cov=want_cov)
-
-
-def _conditional_gaussian_host(precision, mean, observed_mask, observed_values, clip01, dev):
-    """D beyond what the device covers (uglad_conditional_mean_wide, D <= max_dim = 2048): the reference's own formulation on the host in
-    float64 (ref main.py:1176-1227: mean_u - L_uu^-1 L_uo (x_o - mean_o), conditional covariance L_uu^-1, the density at the MAP point), returned
-    in the layout of the device entry point (full mean; L_uu^-1 on the unobserved block, identity elsewhere; log density)."""
-    to64 = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)  # noqa: E731
-    P, mu, mask, vals = to64(precision), to64(mean), to64(observed_mask) != 0, to64(observed_values)
-    K, D = mu.shape
-    full, cov, logp = np.empty((K, D)), np.empty((K, D, D)), np.empty(K)
-    for k in range(K):
-        o, u = np.where(mask[k])[0], np.where(~mask[k])[0]
-        Luu_inv = np.linalg.inv(P[k][np.ix_(u, u)]) if u.size else np.zeros((0, 0))
-        m = mu[k].copy()
-        m[o] = vals[k][o]
-        if u.size:
-            m[u] = mu[k][u] - Luu_inv @ (P[k][np.ix_(u, o)] @ (vals[k][o] - mu[k][o]))
-        if clip01:
-            m = np.clip(m, 0.0, 1.0)
-        full[k] = m
-        cov[k] = np.eye(D)
-        cov[k][np.ix_(u, u)] = Luu_inv
-        # density of the conditional Gaussian at its own mean: (2 pi)^(-n_u / 2) det(L_uu)^(1/2)
-        sign, ld = np.linalg.slogdet(P[k][np.ix_(u, u)]) if u.size else (1.0, 0.0)
-        logp[k] = -0.5 * u.size * np.log(2.0 * np.pi) + 0.5 * ld if sign > 0 else np.nan
-    t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev)  # noqa: E731
-    return t(full), t(cov), t(logp)
-
-
-def conditional_gaussian_with_probabilities(precision, mean, observed_idx, observed_values):
-    """Conditional mean, conditional covariance and density at the MAP point of a Gaussian given observed coordinates
-    (ref main.py:1176-1227, same arguments and return values): (full_mean (n,), conditional_cov (n_u, n_u), pdf).
-    The reference solves with scipy on the host; here the path's eigensolver does it on the device (fp32), and beyond its size the fp64
-    Cholesky of uglad_conditional_mean_wide: the density is the exponential of its fp64 logarithm."""
-    precision = np.asarray(precision)
-    mean = np.asarray(mean, dtype=np.float64)
-    n = len(mean)
-    observed_idx = [int(i) for i in observed_idx]
-    mask = np.zeros(n, dtype=np.float32)
-    mask[observed_idx] = 1.0
-    vals = np.zeros(n, dtype=np.float64)
-    vals[observed_idx] = np.asarray(observed_values, dtype=np.float64)
-    full, cov, logp = _conditional_gaussian_device(precision[None], mean[None], mask[None], vals[None], False, True)
-    unobs = [i for i in range(n) if mask[i] == 0.0]
-    cov = cov[0].cpu().numpy().astype(np.float64)
-    return full[0].cpu().numpy().astype(np.float64), cov[np.ix_(unobs, unobs)], float(np.exp(np.float64(logp[0].item())))
-
-
-def compute_map_estimate(observed_nodes: dict, model_uGLAD) -> np.ndarray:
-    """MAP estimate of all nodes given some observed ones, clamped to [0, 1] (ref main.py:1229-1260): uses the estimator's
-    precision_, location_ and node_names_."""
-    names = list(model_uGLAD.node_names_)
-    idx = [names.index(k) for k in observed_nodes.keys()]
-    n = len(names)
-    mask = np.zeros(n, dtype=np.float32)
-    mask[idx] = 1.0
-    vals = np.zeros(n, dtype=np.float64)
-    vals[idx] = list(observed_nodes.values())
-    full, _, _ = conditional_gaussian_batch(np.asarray(model_uGLAD.precision_)[None], np.asarray(model_uGLAD.location_)[None],
-                                            mask[None], vals[None], clip01=True, want_cov=False)
-    return full[0].cpu().numpy().astype(np.float64)
 
 
 def save_uGLAD_model(obj, filepath: str) -> None:
