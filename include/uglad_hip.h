@@ -361,6 +361,32 @@ int uglad_rank_correlation_pair_chunks(int K, int N, int D);
 int uglad_rank_correlation(const double* X, int K, int N, int D, int method, int transform, double eval_offset, float* A_out,
                            double* A64_out, double* gram_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
 
+/* The available-case (pairwise-complete) covariance of K tables with missing entries, and the repair on it (csrc/pairwise_wide.h; what
+ * pandas' DataFrame.cov and R's cov(use = "pairwise.complete.obs") compute, with the reference's divisor).  X is a DEVICE pointer to
+ * (K, N, D) row-major FP64 tables; only NaN counts as missing.  With m_ni = 1 where x_ni is observed, y = x (normalize = 0) or
+ * y = (x - mn_i) * (1 / (mx_i - mn_i)) over the observed minimum and maximum of column i (normalize = 1), mu_i the mean of the observed
+ * y_.i and z_ni = m_ni (y_ni - mu_i):  n_ij = sum_n m_ni m_nj, a_ij = sum_n z_ni m_nj, p_ij = sum_n z_ni z_nj and
+ *   cov_ij = p_ij / n_ij - (a_ij / n_ij) (a_ji / n_ij),
+ * the covariance of the n_ij rows where both columns are observed, every mean taken over those rows, divided by n_ij (pandas' value times
+ * (n_ij - 1) / n_ij).  The shift by mu_i keeps a column offset from cancelling; mu_i is the implementation's rounding of the observed
+ * mean ((sum of the observed x / their number - mn_i) * scale), which the result depends on by rounding alone.  Every sum has a fixed
+ * order: two calls give the same bits, and they do not depend on K or on the table's place in the batch.  S_out (K, D, D) fp32 receives the
+ * matrix, exactly symmetric; S64_out (K, D, D) fp64, optional, the same before the one rounding and ALWAYS unrepaired; counts_out
+ * (K, D, D) int32, optional, n_ij; info_out (K, D) int32, optional, per column: bit 1 the column has no observed entry; 2 it is in a pair
+ * with n_ij < min_pairs (that entry is NaN; pairs with a column flagged 1, 4 or 8 do not count); 4 normalize = 1 and its observed values
+ * are constant (0 / 0, as the reference's NaN); 8 it holds an infinity, which is a value and propagates.  A column flagged 1, 4 or 8 has
+ * NaN in its row and column.  min_eig_out NULL: no repair.  Otherwise (K doubles), as uglad_association -- the matrix is in general
+ * indefinite, every entry having its own set of rows --: a table whose smallest eigenvalue is <= 1e-6 gets S_out += (eval_offset - min
+ * eig) I and min_eig_out[k] = that eigenvalue, by 48 bisection steps over [-||S||_inf, 1e-6]; a table that passes at 1e-6 gets
+ * +infinity; a table with any flag set is not repaired and gets NaN, at the cost of empty launches.  Many workgroups per table,
+ * 3 + 52 + 49 * 2 ceil(D / 64) + 2 launches, no host readback, no allocation.  workspace: uglad_pairwise_covariance_workspace_floats(K, D)
+ * floats, 8-byte aligned (UGLAD_E_NULL otherwise): per table uglad_covariance_wide's slabs and D rounded up to 64, plus 2, int32 of
+ * flags.  1 <= D <= uglad_max_dim(), N >= 1, K <= 65535 (UGLAD_E_DIM otherwise); normalize not 0 / 1 or min_pairs < 1 gives UGLAD_E_MODE;
+ * the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+int uglad_pairwise_covariance_workspace_floats(int K, int D);
+int uglad_pairwise_covariance(const double* X, int K, int N, int D, int normalize, int min_pairs, double eval_offset, float* S_out,
+                              double* S64_out, int* counts_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
+
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
  * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k, the rows without one (D-2, D-1) are
  * zero; workspace receives d, e, tau

@@ -23,6 +23,7 @@ from .main import (  # noqa: F401
     recovered_graph,
     mixed_association,
     rank_correlation,
+    pairwise_covariance,
     graph_from_partial_correlations,
     compute_graph_statistics,
     RecoveredGraph,
@@ -35,6 +36,6 @@ from .main import (  # noqa: F401
     load_uGLAD_model,
 )
 from .utils.prepare_data import cramers_v, correlation_ratio, pairwise_cov_matrix, encode_mixed_table  # noqa: F401
-from .utils.prepare_data import rank_correlation_host  # noqa: F401
+from .utils.prepare_data import rank_correlation_host, pairwise_covariance_host  # noqa: F401
 
 __version__ = "0.1.0"

@@ -71,6 +71,9 @@ _SIGS = {
     "uglad_rank_correlation_pair_chunks": ([ctypes.c_int] * 3, ctypes.c_int),
     "uglad_rank_correlation": ([ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_double, _c_float_p] + [ctypes.c_void_p] * 4
                                + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_pairwise_covariance_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_pairwise_covariance": ([ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_double, _c_float_p] + [ctypes.c_void_p] * 4
+                                  + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
@@ -130,6 +133,19 @@ class RankCorrelation(NamedTuple):
     A64: Optional[torch.Tensor]       # (K, D, D) float64, unrepaired
     gram: Optional[torch.Tensor]      # (K, D, D) float64
     info: torch.Tensor                # (K, D) int32: bit 0 NaN, bit 1 constant
+
+
+class PairwiseCovariance(NamedTuple):
+    """What uglad_pairwise_covariance leaves on the device for K tables (include/uglad_hip.h)."""
+    S: torch.Tensor                   # (K, D, D) float32, repaired when asked
+    S64: Optional[torch.Tensor]       # (K, D, D) float64, unrepaired
+    counts: Optional[torch.Tensor]    # (K, D, D) int32: the jointly observed rows of every pair
+    info: torch.Tensor                # (K, D) int32: PAIRWISE_FLAGS
+    min_eig: Optional[torch.Tensor]   # (K,) float64, +inf for a table that needed no repair, NaN for a flagged one
+
+
+PAIRWISE_FLAGS = {1: "no observed entry", 2: "in a pair with fewer than min_pairs jointly observed rows",
+                  4: "constant observed values under normalize", 8: "holds an infinity"}
 
 
 class HipLib:
@@ -435,6 +451,28 @@ class HipLib:
         self._call("uglad_rank_correlation", self._vp(X64), K, N, D, int(m), int(bool(transform)), float(eval_offset), self._p(A),
                    self._vp(A64), self._vp(gram), self._vp(info), self._vp(mn), self._p(wsp))
         return RankCorrelation(A, mn, A64, gram, info)
+
+    def pairwise_covariance(self, X64, normalize: bool = False, min_pairs: int = 2, eval_offset: float = 0.1, repair: bool = True,
+                            want_f64: bool = False, want_counts: bool = False) -> "PairwiseCovariance":
+        """(K,N,D) FLOAT64 tables on the device, NaN = missing -> PairwiseCovariance (uglad_pairwise_covariance): the available-case
+        covariance, every entry over the rows where both its columns are observed (divided by their number n_ij), of the columns as they
+        are or, with `normalize`, min-max normalised over their observed entries.  S (K,D,D) fp32, repaired like a covariance when
+        `repair`; S64 (K,D,D) fp64 unrepaired (None without `want_f64`); counts (K,D,D) int32, n_ij (None without `want_counts`); info
+        (K,D) int32, the bits of PAIRWISE_FLAGS -- an entry with n_ij < min_pairs and the row and column of a column flagged 1, 4 or 8
+        are NaN --; min_eig (K,) fp64: the smallest eigenvalue before the repair, +inf for a table that needed none, NaN for a table with
+        any flag set, which is not repaired (None without `repair`)."""
+        self._require_f64(X64, 3, "pairwise_covariance takes a contiguous (K, N, D) float64 tensor")
+        K, N, D = X64.shape
+        dev = X64.device
+        wsp = self._wide_workspace("uglad_pairwise_covariance", dev, K, D)
+        S = torch.empty(K, D, D, dtype=torch.float32, device=dev)
+        S64 = torch.empty(K, D, D, dtype=torch.float64, device=dev) if want_f64 else None
+        counts = torch.empty(K, D, D, dtype=torch.int32, device=dev) if want_counts else None
+        info = torch.empty(K, D, dtype=torch.int32, device=dev)
+        mn = torch.empty(K, dtype=torch.float64, device=dev) if repair else None
+        self._call("uglad_pairwise_covariance", self._vp(X64), K, N, D, int(bool(normalize)), int(min_pairs), float(eval_offset), self._p(S),
+                   self._vp(S64), self._vp(counts), self._vp(info), self._vp(mn), self._p(wsp))
+        return PairwiseCovariance(S, S64, counts, info, mn)
 
     def rank_pair_chunks(self, K: int, N: int, D: int) -> int:
         """The number of chunks a Kendall call of this shape deals the row pairs of a tile over (uglad_rank_correlation_pair_chunks)."""

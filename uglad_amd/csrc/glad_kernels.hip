@@ -44,6 +44,7 @@ namespace uglad {
 #include "cov_wide.h"
 #include "assoc_wide.h"
 #include "rank_wide.h"
+#include "pairwise_wide.h"
 #include "after_wide.h"
 #include "score_wide.h"
 #include "sort_wide.h"

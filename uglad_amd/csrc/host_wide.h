@@ -20,16 +20,23 @@ static void launch_cholw(hipStream_t st, int K, const View& v) {
   }
 }
 // the shift bisection of K slabs and their repair (chol_wide.h): the test at the threshold, then Bracket::kSteps steps; slabs that are done
-// (or whose factorisation has broken down) cost empty launches.  out32: the (K, D, D) fp32 matrix whose diagonal the repair rewrites
-template <class Bracket>
-static void launch_cholw_bisection(hipStream_t st, int K, int D, double eval_offset, const CholwView& v, float* out32, double* min_eig_out) {
+// (or whose factorisation has broken down) cost empty launches.  out32: the (K, D, D) fp32 matrix whose diagonal the repair rewrites.
+// after_reset(): the client's launches between the controller's reset and the first factorisation (a client that bars slabs of its own)
+template <class Bracket, class AfterReset>
+static void launch_cholw_bisection(hipStream_t st, int K, int D, double eval_offset, const CholwView& v, float* out32, double* min_eig_out,
+                                   AfterReset after_reset) {
   constexpr int steps = Bracket::kSteps;
   for (int step = 0; step <= steps; ++step) {
     hipLaunchKernelGGL(cholw_bisect_kernel<Bracket>, dim3(K), dim3(64), 0, st, step - 1, D, v);
+    if (step == 0) after_reset();
     launch_cholw(st, K, v);
   }
   hipLaunchKernelGGL(cholw_bisect_kernel<Bracket>, dim3(K), dim3(64), 0, st, steps, D, v);
   hipLaunchKernelGGL(cholw_repair_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, eval_offset, v, out32, min_eig_out);
+}
+template <class Bracket>
+static void launch_cholw_bisection(hipStream_t st, int K, int D, double eval_offset, const CholwView& v, float* out32, double* min_eig_out) {
+  launch_cholw_bisection<Bracket>(st, K, D, eval_offset, v, out32, min_eig_out, [] {});
 }
 // the radix sort of K arrays of keys (sort_wide.h); an even number of passes: the sorted keys end in buffer 0
 static void launch_sortw(hipStream_t st, int K, const SortwView& v) {
@@ -213,6 +220,29 @@ int uglad_rank_correlation(const double* X, int K, int N, int D, int method, int
   if (!min_eig_out) return launch_status();  // no repair
   hipLaunchKernelGGL(assoc_rowsum_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, v.c);
   launch_cholw_bisection<AssocBracket>(st, K, D, eval_offset, v.c, A_out, min_eig_out);
+  return launch_status();
+}
+
+int uglad_pairwise_covariance_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, pairw_table_floats); }
+
+int uglad_pairwise_covariance(const double* X, int K, int N, int D, int normalize, int min_pairs, double eval_offset, float* S_out,
+                              double* S64_out, int* counts_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream) {
+  if (!X || !S_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_pairwise_covariance_workspace_floats(K, D) < 0 || N < 1) return UGLAD_E_DIM;
+  if ((normalize != 0 && normalize != 1) || min_pairs < 1) return UGLAD_E_MODE;
+  hipStream_t st = (hipStream_t)stream;
+  const PairwView v = pairw_view(workspace, D);
+  const int nt = v.c.DP / kT64;
+  const dim3 wg(kWThreads);
+  hipLaunchKernelGGL(pairw_stats_kernel, dim3(nt, K), wg, 0, st, X, N, D, normalize, v);
+  hipLaunchKernelGGL(pairw_gram_kernel, dim3(nt, nt, K), wg, 0, st, X, N, D, min_pairs, v, PairwOut{S_out, S64_out, counts_out});
+  hipLaunchKernelGGL(pairw_info_kernel, dim3(K), wg, 0, st, D, v, info_out);
+  if (!min_eig_out) return launch_status();  // no repair
+  // as uglad_association, on the bracket of an indefinite matrix; a flagged table (it holds NaN) is barred behind the controller's reset
+  hipLaunchKernelGGL(assoc_rowsum_kernel, dim3((D + 255) / 256, K), dim3(256), 0, st, D, v.c);
+  launch_cholw_bisection<AssocBracket>(st, K, D, eval_offset, v.c, S_out, min_eig_out,
+                                       [&] { hipLaunchKernelGGL(pairw_bar_kernel, dim3(K), dim3(64), 0, st, 0, v, min_eig_out); });
+  hipLaunchKernelGGL(pairw_bar_kernel, dim3(K), dim3(64), 0, st, 1, v, min_eig_out);
   return launch_status();
 }
 

@@ -1,10 +1,11 @@
 """How a table becomes the matrix the path runs on: the covariance (host fp64 like the reference's prepare_data.get_covariance, or under
 `device_covariance` the device front-ends uglad_covariance / uglad_covariance_wide), the association matrix of a mixed table
-(uglad_association) and the rank correlations of the nonparanormal model (uglad_rank_correlation).  `uglad_amd.main` re-exports the
-public names."""
+(uglad_association), the rank correlations of the nonparanormal model (uglad_rank_correlation) and the pairwise-complete covariance of a
+table with missing entries (uglad_pairwise_covariance).  `uglad_amd.main` re-exports the public names."""
 from __future__ import annotations
 
 import contextlib
+import warnings
 
 import numpy as np
 import torch
@@ -103,14 +104,20 @@ def mixed_association(df, dtype, repair: bool = True, eval_offset: float = 0.1):
     return A[0], (None if mn is None else float(mn[0]))
 
 
-def _rank_tables(X):
+def _stacked_tables(X, what: str):
     """(tables (K, N, D) float64 contiguous, single, names): an (N, D) array or DataFrame, or a list / (K, N, D) array of tables."""
     names = [str(c) for c in X.columns] if hasattr(X, "columns") else None
     single = hasattr(X, "columns") or (not isinstance(X, (list, tuple)) and np.ndim(X) == 2)
     tables = np.array(X, dtype=np.float64, order="C")  # (a copy of its own: the caller's array may be read-only)
     tables = tables[None] if single else tables
     if tables.ndim != 3:
-        raise ValueError("rank_correlation takes an (N, D) table, or a list / (K, N, D) array of tables of one shape")
+        raise ValueError(f"{what} takes an (N, D) table, or a list / (K, N, D) array of tables of one shape")
+    return tables, single, names
+
+
+def _rank_tables(X):
+    """_stacked_tables for the rank correlations, which have no meaning for a NaN."""
+    tables, single, names = _stacked_tables(X, "rank_correlation")
     if np.isnan(tables).any():
         raise ValueError("rank_correlation: the table holds NaN; impute or drop those rows first")
     return tables, single, names
@@ -132,3 +139,34 @@ def rank_correlation(X, method: str = "kendall", transform: bool = True, repair:
         return out.A[0], (None if mn is None else float(mn[0]))
     return out.A, mn
 
+
+def pairwise_flag_message(info, names=None) -> str:
+    """What the flag words of one table (uglad_pairwise_covariance's info_out, (D,) int32) say, column by column; "" when none is set."""
+    info = np.asarray(info)
+    names = names if names is not None else [f"node_{i}" for i in range(len(info))]
+    parts = [f"{[names[i] for i in np.nonzero(info & bit)[0]]}: {why}" for bit, why in _lib.PAIRWISE_FLAGS.items() if (info & bit).any()]
+    return "; ".join(parts)
+
+
+def pairwise_covariance(X, normalize: bool = False, repair: bool = True, eval_offset: float = 0.1, min_pairs: int = 2):
+    """The available-case (pairwise-complete) covariance of a table with missing entries (NaN), on the device (uglad_pairwise_covariance,
+    csrc/pairwise_wide.h; additive -- the reference imputes column means, which shrinks every covariance --, what pandas' DataFrame.cov
+    and R's cov(use = "pairwise.complete.obs") offer, divided by n_ij like the reference's covariance by N): entry (i, j) over the rows
+    where columns i and j are both observed; with `normalize` of the columns min-max normalised over their observed entries.  X is an
+    (N, D) array or DataFrame, or a list / (K, N, D) array of tables of one shape.  Returns (S, min_eig, counts): S the (D, D) -- or
+    (K, D, D) -- fp32 matrix on the device, with `repair` shifted like a covariance (min eig <= 1e-6: S += (eval_offset - min eig) I; the
+    matrix is in general indefinite); min_eig the smallest eigenvalue before the repair as a float -- or a (K,) float64 array -- (+inf
+    where none was needed; None without `repair`); counts the int32 device tensor of the n_ij.  An entry with n_ij < min_pairs is NaN, as
+    are the row and column of a column that is never observed, constant under `normalize`, or holds an infinity; such a table is not
+    repaired and its min_eig is NaN; a RuntimeWarning names its columns and says why (HipLib.pairwise_covariance returns the flag words)."""
+    tables, single, names = _stacked_tables(X, "pairwise_covariance")
+    out = _lib.get_lib().pairwise_covariance(torch.from_numpy(tables).to(_lib.device()), normalize=normalize, min_pairs=min_pairs,
+                                             eval_offset=eval_offset, repair=repair, want_counts=True)
+    for k, info in enumerate(out.info.cpu().numpy()):
+        if info.any():
+            warnings.warn(f"pairwise_covariance: table {k} holds NaN and is not repaired: {pairwise_flag_message(info, names)}",
+                          RuntimeWarning, stacklevel=2)
+    mn = None if out.min_eig is None else out.min_eig.cpu().numpy()
+    if single:
+        return out.S[0], (None if mn is None else float(mn[0])), out.counts[0]
+    return out.S, mn, out.counts

@@ -32,7 +32,8 @@ from .dist import Collective, get_collective
 from .glad import glad
 from .glad.glad_params import GladParams
 from .inputs import (  # noqa: F401  (how a table becomes the input matrix: uglad_amd/inputs.py)
-    _covariance, _rank_tables, _to_dev, device_covariance, mixed_association, rank_correlation)
+    _covariance, _rank_tables, _stacked_tables, _to_dev, device_covariance, mixed_association, pairwise_covariance, pairwise_flag_message,
+    rank_correlation)
 from .utils import prepare_data
 from .utils.metrics import report_metrics_all  # noqa: F401  (host-side API parity; the drivers count on the device)
 
@@ -674,6 +675,74 @@ class uGLAD_GL(_Estimator):
         self.data_min_ = self.data_range_ = None  # (rows of a copula fit are not scored)
         self.node_names_ = names
         cond_max = regime.warn_if_outside("uGLAD_GL.fit_copula", None)
+        return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+
+    def fit_pairwise(self, X, true_theta=None, eval_offset=0.1, epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True, sqrt_mode=None,
+                     min_pairs=2, k_fold=0):
+        """`fit` for a table with missing entries (NaN) without imputing them (additive; `fit` fills every NaN with the column mean, as
+        the reference does, which shrinks every covariance): the table is min-max normalised over its observed entries and its
+        available-case (pairwise-complete) covariance -- entry (i, j) over the rows where both columns are observed -- is formed and
+        repaired on the device (uglad_pairwise_covariance, pairwise_covariance); training runs on that matrix.  X is an (N, D) array or
+        DataFrame; no row or column is dropped.  k_fold = 0: direct mode.  k_fold >= 2: the reference's missing-mode ensemble
+        (run_uGLAD_missing) on pairwise matrices -- the k_fold row folds of the table with its NaN kept, one matrix each (one device call
+        per group of folds of one shape), one shared model trained on that batch with the loss against the full table's matrix, the
+        consensus get_final_precision_from_batch(type="min") at the end; on one device only.  A column that is never observed, constant,
+        infinite, or observed together with another in fewer than `min_pairs` rows -- in the table or in a fold -- raises ValueError.
+        Sets covariance_ (the UNREPAIRED matrix, float64), precision_, location_ (the observed means in the model's coordinates),
+        data_min_ / data_range_ (of the observed entries: mahalanobis / score_samples work afterwards, NaN for a row that holds a NaN),
+        node_names_, model_glad, cond_max_, pairwise_min_eig_ and pairwise_counts_ ((D, D) int: the rows behind every entry);
+        predict(S=...), recovered_graph() and save / load work afterwards."""
+        start = time()
+        if verbose:
+            print("Running uGLAD on a pairwise-complete covariance")
+        tables, single, names = _stacked_tables(X, "fit_pairwise")
+        if not single:
+            raise ValueError("fit_pairwise takes one (N, D) table")
+        if k_fold != 0 and get_collective().world_size > 1:
+            raise ValueError("fit_pairwise(k_fold=...) is not sharded over ranks: run it in one process")
+        table = tables[0]
+        N, D = table.shape
+        names = names if names is not None else [f"node_{i}" for i in range(D)]
+        lib = _lib.get_lib()
+
+        def matrices(group, what):
+            out = lib.pairwise_covariance(torch.from_numpy(np.ascontiguousarray(group)).to(_lib.device()), normalize=True,
+                                          min_pairs=min_pairs, eval_offset=eval_offset, repair=True, want_f64=True, want_counts=True)
+            for k, info in enumerate(out.info.cpu().numpy()):
+                if info.any():
+                    raise ValueError(f"fit_pairwise: {what(k)} has no pairwise-complete covariance: {pairwise_flag_message(info, names)}")
+            return out
+
+        full = matrices(tables, lambda k: "the table")
+        if k_fold == 0:
+            pred_theta, compare_theta, model_glad, regime = self._train_direct_on(full.S, true_theta, eval_offset, epochs, lr, INIT_DIAG, L,
+                                                                                  verbose, sqrt_mode)
+        else:
+            folds = [table[train] for train, _ in _kfold_indices(N, k_fold)]
+            groups = {}
+            for i, fold in enumerate(folds):
+                groups.setdefault(fold.shape, []).append(i)
+            S_K = torch.empty(k_fold, D, D, dtype=torch.float32, device=_lib.device())
+            for idx in groups.values():
+                S_K[idx] = matrices(np.stack([folds[i] for i in idx]), lambda k: f"fold {idx[k]}").S
+            one = Collective()
+            with glad.regime_monitor() as regime:
+                pred_theta, model_glad = _train_sharded(S_K, one, k_fold, epochs, lr, INIT_DIAG, L, verbose, sqrt_mode, loss_Sb=full.S)
+                pred_theta = get_final_precision_from_batch(pred_theta, type="min", collective=one)
+            compare_theta = None
+            if true_theta is not None:
+                compare_theta = device_report_metrics(_to_dev(np.asarray(true_theta).reshape(1, D, D)), pred_theta[:1])[0]
+                if verbose:
+                    print(f"Comparison - {compare_theta}")
+        mn, scale = prepare_data.observed_min_scale(table)
+        self.covariance_ = full.S64[0].cpu().numpy()
+        self.pairwise_min_eig_ = float(full.min_eig[0])
+        self.pairwise_counts_ = full.counts[0].cpu().numpy()
+        self.location_ = np.nanmean((table - mn) * scale, axis=0)
+        self.data_min_, self.data_range_ = mn, np.nanmax(table, axis=0) - mn
+        self.node_names_ = names
+        cond_max = regime.warn_if_outside("uGLAD_GL.fit_pairwise", None)
         return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
                                 L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
 

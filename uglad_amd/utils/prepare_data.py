@@ -611,6 +611,49 @@ def rank_correlation_host(X, method: str, transform: bool = True) -> np.ndarray:
     return A
 
 
+# --------------------------------------------------------------------------- tables with missing entries
+def observed_min_scale(X):
+    """(min, 1 / (max - min)) over the observed (not NaN) entries of every column of an (N, D) table, float64: the min-max map of
+    uglad_pairwise_covariance under normalize = 1, y = (x - min) * scale.  NaN for a column without an observed entry."""
+    X = np.asarray(X, dtype=np.float64)
+    seen = ~np.isnan(X)
+    mn = np.where(seen, X, np.inf).min(axis=0)
+    mx = np.where(seen, X, -np.inf).max(axis=0)
+    empty = ~seen.any(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(empty, np.nan, mn), np.where(empty, np.nan, 1.0 / (mx - mn))
+
+
+def pairwise_covariance_host(X, normalize: bool = False, min_pairs: int = 2):
+    """The available-case (pairwise-complete) covariance of an (N, D) table whose NaN are missing entries, as uglad_pairwise_covariance
+    defines it (include/uglad_hip.h, csrc/pairwise_wide.h; additive: the reference imputes column means), vectorised fp64 numpy: the
+    tests' oracle and the probe's baseline.  With m = 1 where observed, y = x or (`normalize`) the column min-max normalised over its
+    observed entries, z = m (y - the observed mean): cov_ij = p_ij / n_ij - (a_ij / n_ij) (a_ji / n_ij) with n = m^T m, a = z^T m,
+    p = z^T z -- pandas' DataFrame.cov times (n_ij - 1) / n_ij.  Returns (cov (D, D) float64, exactly symmetric, NaN where n_ij <
+    min_pairs and wherever the arithmetic gives it: a column that is all NaN, constant under `normalize`, or holds an infinity; counts
+    (D, D) int64, n_ij)."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("pairwise_covariance_host takes one (N, D) table")
+    if min_pairs < 1:
+        raise ValueError(f"min_pairs must be at least 1, got {min_pairs}")
+    seen = ~np.isnan(X)
+    m = seen.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        y = X
+        if normalize:
+            mn, scale = observed_min_scale(X)
+            y = (X - mn) * scale
+        count = m.sum(axis=0)
+        mu = np.where(seen, y, 0.0).sum(axis=0) / count
+        z = np.where(seen, y - mu, 0.0)
+        n, a, p = m.T @ m, z.T @ m, z.T @ z
+        cov = p / n - (a / n) * (a.T / n)
+    cov[n < min_pairs] = np.nan
+    cov = np.triu(cov) + np.triu(cov, 1).T  # (the mirror is a copy, as on the device)
+    return cov, np.rint(n).astype(np.int64)
+
+
 # --------------------------------------------------------------------------- bench inputs
 def synthetic_covariance_batch(
     num_tasks: int,
