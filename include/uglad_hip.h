@@ -387,6 +387,29 @@ int uglad_pairwise_covariance_workspace_floats(int K, int D);
 int uglad_pairwise_covariance(const double* X, int K, int N, int D, int normalize, int min_pairs, double eval_offset, float* S_out,
                               double* S64_out, int* counts_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
 
+/* The covariances of ONE table under R weightings of its rows, and the repair on each (csrc/wcov_wide.h; additive: what resampling needs
+ * -- a bootstrap resample is a weighting by integer multiplicities, a subsample or a fold one by 0 / 1, a smoothing window one by real
+ * weights).  The caller defines X, a DEVICE pointer to the (N, D) row-major FP64 table, and W, a DEVICE pointer to (R, N) FP64 weights;
+ * both are only read.  For weighting r, with s = sum_n w_n and mu = sum_n w_n x_n / s:
+ *   S = sum_n w_n (x_n - mu) (x_n - mu)^T / s,
+ * empirical_covariance of the table with row n repeated w_n times (integer weights), of the row subset (0 / 1), of the table (all ones).
+ * There is no normalisation: the caller normalises the table once.  The table is shifted by its unweighted column means c, so that one
+ * staged chunk of it serves several weightings, and S = G / s - d d^T with G the weighted Gram matrix of x - c and d = mu - c.  Every sum
+ * has a fixed order: two calls give the same bits, and a weighting's bits do not depend on R or on its place in the call.  The entry
+ * point defines every element of its outputs: S_out (R, D, D) fp32, exactly symmetric; S64_out (R, D, D) fp64, optional, the same before
+ * the one rounding and ALWAYS unrepaired; mean_out (R, D) fp64, optional, mu; info_out (R) int32, per weighting: bit 1 a weight is
+ * negative, NaN or infinite; 2 the weights sum to zero.  A flagged weighting is NaN throughout S_out, S64_out and mean_out and leaves
+ * the others' bits alone.  A NaN or an infinity in X propagates into that column's row and column of every weighting.  min_eig_out NULL:
+ * no repair.  Otherwise (R doubles), as uglad_covariance_wide per weighting: smallest eigenvalue <= 1e-6 gives S_out += (eval_offset -
+ * min eig) I and min_eig_out[r] = that eigenvalue; a weighting that passes at 1e-6 gets +infinity; a flagged one is not repaired and
+ * gets NaN, at the cost of empty launches.  3 + 25 (2 ceil(D / 64) + 1) + 4 launches, no host readback, no allocation.  workspace:
+ * uglad_weighted_covariance_workspace_floats(R, D) floats, 8-byte aligned (UGLAD_E_NULL otherwise), scratch: per weighting
+ * uglad_covariance_wide's slabs and D rounded up to 64, plus 2, doubles of its sums.  1 <= D <= uglad_max_dim(), N >= 1, 1 <= R <= 65535
+ * (UGLAD_E_DIM otherwise); the workspace size is negative (UGLAD_E_DIM) on bad arguments or beyond 2^31 - 1 floats. */
+int uglad_weighted_covariance_workspace_floats(int R, int D);
+int uglad_weighted_covariance(const double* X, const double* W, int R, int N, int D, double eval_offset, float* S_out, double* S64_out,
+                              double* mean_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream);
+
 /* First half of the eigensolver on its own (unit tests, profiling): Householder tridiagonalisation of A = A0 (A1 == NULL) or
  * A = A0/lam[0] - A1 (the cell's b = S/lam - Z).  Row k of R_m (M, D, D) receives reflector v_k, the rows without one (D-2, D-1) are
  * zero; workspace receives d, e, tau
@@ -492,6 +515,17 @@ int uglad_graph_wide_workspace_floats(int K, int D);
 int uglad_graph_wide(const float* values, int from_precision, const int* n_keep, const float* threshold_in, float* threshold,
                      int* edge_count, int* edge_ij, float* edge_w, int* degree, int* triangles2, double* stats, int want_stats, int K, int D,
                      float* workspace, uglad_stream_t stream);
+
+/* How often every edge comes back over R recovered graphs (csrc/graph_wide.h; the selection frequencies of stability selection, StARS'
+ * instability).  The inputs are what uglad_graph_wide leaves for K = R problems of dimension D, defined by that call and only read here:
+ * edge_count (R), edge_ij (R, E, 2), edge_w (R, E), E = D (D - 1) / 2; only the first edge_count[r] entries of list r are read.  The entry
+ * point defines every element of its outputs and zeroes them itself: count_out (D, D) int32, count_out[i][j] = count_out[j][i] = the
+ * number of lists that hold edge {i, j}, zero on the diagonal; positive_out (D, D) int32, the same count over the edges with weight > 0;
+ * totals_out (2) 64-bit integers = {sum_{i < j} c_ij, sum_{i < j} c_ij (R - c_ij)}, exact.  Integer atomics only: the output does not
+ * depend on the order of the additions.  No workspace; 4 launches, no host readback.  2 <= D <= uglad_max_dim(), 1 <= R <= 65535
+ * (UGLAD_E_DIM otherwise); a NULL pointer gives UGLAD_E_NULL. */
+int uglad_edge_frequency(const int* edge_count, const int* edge_ij, const float* edge_w, int R, int D, int* count_out, int* positive_out,
+                         long long* totals_out, uglad_stream_t stream);
 
 /* All eigenvalues of K symmetric matrices, every 1 <= D <= uglad_max_dim(), values only, fp64 throughout, many workgroups per matrix
  * (csrc/eigvals_wide.h): a blocked Householder tridiagonalisation (panels of 64, the trailing updates on the fp64 MFMA) and Sturm-count

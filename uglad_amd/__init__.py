@@ -24,6 +24,8 @@ from .main import (  # noqa: F401
     mixed_association,
     rank_correlation,
     pairwise_covariance,
+    weighted_covariance,
+    edge_frequency,
     graph_from_partial_correlations,
     compute_graph_statistics,
     RecoveredGraph,
@@ -37,5 +39,6 @@ from .main import (  # noqa: F401
 )
 from .utils.prepare_data import cramers_v, correlation_ratio, pairwise_cov_matrix, encode_mixed_table  # noqa: F401
 from .utils.prepare_data import rank_correlation_host, pairwise_covariance_host  # noqa: F401
+from .utils.prepare_data import weighted_covariance_host, resample_weights  # noqa: F401
 
 __version__ = "0.1.0"

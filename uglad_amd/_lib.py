@@ -74,6 +74,10 @@ _SIGS = {
     "uglad_pairwise_covariance_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "uglad_pairwise_covariance": ([ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_double, _c_float_p] + [ctypes.c_void_p] * 4
                                   + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_weighted_covariance_workspace_floats": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "uglad_weighted_covariance": ([ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_double, _c_float_p] + [ctypes.c_void_p] * 4
+                                  + [_c_float_p, ctypes.c_void_p], ctypes.c_int),
+    "uglad_edge_frequency": ([ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4, ctypes.c_int),
     "uglad_tridiagonalize": ([_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_symeig_jacobi": ([_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "uglad_conditional_mean": ([_c_float_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
@@ -142,6 +146,25 @@ class PairwiseCovariance(NamedTuple):
     counts: Optional[torch.Tensor]    # (K, D, D) int32: the jointly observed rows of every pair
     info: torch.Tensor                # (K, D) int32: PAIRWISE_FLAGS
     min_eig: Optional[torch.Tensor]   # (K,) float64, +inf for a table that needed no repair, NaN for a flagged one
+
+
+class WeightedCovariance(NamedTuple):
+    """What uglad_weighted_covariance leaves on the device for R weightings of one table's rows (include/uglad_hip.h)."""
+    S: torch.Tensor                   # (R, D, D) float32, repaired when asked
+    S64: Optional[torch.Tensor]       # (R, D, D) float64, unrepaired
+    mean: Optional[torch.Tensor]      # (R, D) float64: the weighted column means
+    info: torch.Tensor                # (R,) int32: WEIGHT_FLAGS
+    min_eig: Optional[torch.Tensor]   # (R,) float64, +inf for a weighting that needed no repair, NaN for a flagged one
+
+
+WEIGHT_FLAGS = {1: "a weight is negative, NaN or infinite", 2: "the weights sum to zero"}
+
+
+class EdgeFrequency(NamedTuple):
+    """What uglad_edge_frequency leaves on the device for R recovered graphs (include/uglad_hip.h)."""
+    count: torch.Tensor               # (D, D) int32: the graphs that hold edge {i, j}
+    positive: torch.Tensor            # (D, D) int32: ... with a weight > 0
+    totals: torch.Tensor              # (2,) int64: sum_{i<j} c_ij, sum_{i<j} c_ij (R - c_ij)
 
 
 PAIRWISE_FLAGS = {1: "no observed entry", 2: "in a pair with fewer than min_pairs jointly observed rows",
@@ -473,6 +496,48 @@ class HipLib:
         self._call("uglad_pairwise_covariance", self._vp(X64), K, N, D, int(bool(normalize)), int(min_pairs), float(eval_offset), self._p(S),
                    self._vp(S64), self._vp(counts), self._vp(info), self._vp(mn), self._p(wsp))
         return PairwiseCovariance(S, S64, counts, info, mn)
+
+    def weighted_covariance(self, X64, W64, eval_offset: float = 0.1, repair: bool = True, want_f64: bool = False,
+                            want_mean: bool = False) -> "WeightedCovariance":
+        """ONE (N,D) FLOAT64 table and (R,N) FLOAT64 row weights on the device -> WeightedCovariance (uglad_weighted_covariance): per
+        weighting the covariance sum_n w_n (x_n - mu)(x_n - mu)^T / sum_n w_n about its own weighted mean mu -- a bootstrap resample for
+        integer multiplicities, a subsample for 0 / 1 -- with the table uploaded and staged once for all of them.  S (R,D,D) fp32,
+        repaired like a covariance when `repair`; S64 (R,D,D) fp64 unrepaired (None without `want_f64`); mean (R,D) fp64 (None without
+        `want_mean`); info (R,) int32, the bits of WEIGHT_FLAGS -- a flagged weighting is NaN throughout --; min_eig (R,) fp64: the
+        smallest eigenvalue before the repair, +inf for a weighting that needed none, NaN for a flagged one (None without `repair`)."""
+        self._require_f64(X64, 2, "weighted_covariance takes a contiguous (N, D) float64 table")
+        self._require_f64(W64, 2, "weighted_covariance takes contiguous (R, N) float64 weights")
+        N, D = X64.shape
+        R = W64.shape[0]
+        if W64.shape[1] != N or W64.device != X64.device:
+            raise UgladError(f"weighted_covariance: weights of shape {tuple(W64.shape)} for a table of {N} rows (one device)")
+        dev = X64.device
+        wsp = self._wide_workspace("uglad_weighted_covariance", dev, R, D)
+        S = torch.empty(R, D, D, dtype=torch.float32, device=dev)
+        S64 = torch.empty(R, D, D, dtype=torch.float64, device=dev) if want_f64 else None
+        mean = torch.empty(R, D, dtype=torch.float64, device=dev) if want_mean else None
+        info = torch.empty(R, dtype=torch.int32, device=dev)
+        mn = torch.empty(R, dtype=torch.float64, device=dev) if repair else None
+        self._call("uglad_weighted_covariance", self._vp(X64), self._vp(W64), R, N, D, float(eval_offset), self._p(S), self._vp(S64),
+                   self._vp(mean), self._vp(info), self._vp(mn), self._p(wsp))
+        return WeightedCovariance(S, S64, mean, info, mn)
+
+    def edge_frequency(self, graph: "GraphWide", D: int) -> "EdgeFrequency":
+        """The GraphWide of R problems of dimension D (graph_wide) -> EdgeFrequency (uglad_edge_frequency): per edge the number of the R
+        graphs that hold it, the same over the edges with a positive weight, and the two integer totals StARS' instability is made of."""
+        R, E = graph.edge_w.shape
+        if E != D * (D - 1) // 2 or tuple(graph.edge_ij.shape) != (R, E, 2) or tuple(graph.edge_count.shape) != (R,):
+            raise UgladError(f"edge_frequency: the edge lists are not those of {R} graphs of dimension {D}")
+        for t, dt in ((graph.edge_count, torch.int32), (graph.edge_ij, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous() or (self.require_gpu and not t.is_cuda):
+                raise UgladError("edge_frequency takes the contiguous int32 device tensors graph_wide returns")
+        dev = graph.edge_w.device
+        count = torch.empty(D, D, dtype=torch.int32, device=dev)
+        positive = torch.empty(D, D, dtype=torch.int32, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        self._call("uglad_edge_frequency", self._vp(graph.edge_count), self._vp(graph.edge_ij), self._p(graph.edge_w), R, D, self._vp(count),
+                   self._vp(positive), self._vp(totals))
+        return EdgeFrequency(count, positive, totals)
 
     def rank_pair_chunks(self, K: int, N: int, D: int) -> int:
         """The number of chunks a Kendall call of this shape deals the row pairs of a tile over (uglad_rank_correlation_pair_chunks)."""

@@ -1,6 +1,7 @@
 """Everything after the path, on fitted precision matrices: row scores (uglad_sample_scores), support-recovery metrics
-(uglad_support_metrics*), partial correlations, the recovered graph with its drawing and statistics (uglad_graph_wide), the conditional
-Gaussian and the MAP estimate (uglad_conditional_mean*).  Mirrors the reference's main.py:796-1300; `uglad_amd.main` re-exports the
+(uglad_support_metrics*), partial correlations, the recovered graph with its drawing and statistics (uglad_graph_wide), the edge
+frequencies over the graphs of many resamples (uglad_edge_frequency), the conditional Gaussian and the MAP estimate
+(uglad_conditional_mean*).  Mirrors the reference's main.py:796-1300; `uglad_amd.main` re-exports the
 public names."""
 from __future__ import annotations
 
@@ -231,6 +232,26 @@ def recovered_graph(precision, sparsity: float = 0.1, threshold=None, stats: boo
     n_keep = None if threshold is not None else _n_keep(sparsity, int(P.shape[-1]))
     out = _recovered_graphs(P, True, n_keep, threshold, stats)
     return out[0] if single else out
+
+
+def edge_frequency(precisions, sparsity: float = 0.1):
+    """How often every edge comes back over R precision matrices -- the fits on R resamples of one table -- on the device (additive: the
+    selection frequencies of stability selection and the instability of StARS; uglad_graph_wide for the R graphs at `sparsity`, then
+    uglad_edge_frequency).  (R, D, D), a numpy array or a device tensor -> (frequency, sign_frequency, instability): frequency (D, D)
+    float64 = the number of graphs that hold edge {i, j}, over R (symmetric, zero diagonal); sign_frequency the same over the graphs that
+    hold it with a positive partial correlation; instability = 2 sum_{i<j} c_ij (R - c_ij) / (R^2 E) from exact integer totals, the
+    mean over the E = D (D - 1) / 2 edges of 2 f (1 - f)."""
+    lib = _lib.get_lib()
+    if len(precisions.shape) != 3 or precisions.shape[1] != precisions.shape[2]:
+        raise ValueError("edge_frequency takes (R, D, D) precision matrices")
+    R, D = int(precisions.shape[0]), int(precisions.shape[-1])
+    if D < 2 or D > lib.max_dim:
+        raise ValueError(f"edge_frequency: D = {D} is outside 2 .. {lib.max_dim}")
+    g = lib.graph_wide(_to_dev(precisions), n_keep=_n_keep(sparsity, D), from_precision=True, want_stats=False)
+    out = lib.edge_frequency(g, D)
+    count, positive = out.count.cpu().numpy().astype(np.int64), out.positive.cpu().numpy().astype(np.int64)
+    totals = [int(t) for t in out.totals.cpu().numpy()]
+    return count / R, positive / R, 2 * totals[1] / (R * R * (D * (D - 1) // 2))
 
 
 def graph_from_partial_correlations(rho, names, sparsity=1, title="", fig_size=12, PLOT=True, save_file=None, roundOFF=5):

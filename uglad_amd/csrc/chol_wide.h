@@ -4,7 +4,8 @@
 //
 // The tile layer (t64_): a workgroup of 256 threads owns one 64 x 64 tile; each of its four waves owns a 32 x 32 quadrant as 2 x 2 accumulators
 // f64x4.  The lane-to-element layout of those accumulators is written down ONCE, in t64_for_each_fragment; t64_zero clears them,
-// t64_tile_product fills them, t64_for_each_element is the plain (row, column) sweep of a tile that goes to or from LDS, and
+// t64_tile_product fills them (t64_weighted_tile_products: several sets from one staged chunk; both on t64_tile_sweep, which holds the
+// staging once), t64_for_each_element is the plain (row, column) sweep of a tile that goes to or from LDS, and
 // t64_symmetric_part is a tile of (A + A^T) / 2, symmetric to the bit, for the clients that take a matrix as it was fitted.
 //
 // The factorisation (cholw_): A - sigma I = L L^T, blocked left-looking on 64 x 64 tiles, two launches per block column j:
@@ -89,12 +90,16 @@ __device__ __forceinline__ void t64_symmetric_part(const double* __restrict__ A,
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the tile product
-// acc += sum_k A(x, k) B(y, k) over k0 <= k < k1 on one 64 x 64 tile: the operand layout of ns_gemm64_kernel (lane l supplies
-// A[l & 15][l >> 4], B[l >> 4][l & 15]), the accumulators as above.  Chunks of 32 k go through LDS, the next one prefetched into registers.
+// The sweep of the tile products over k0 <= k < k1: the operand layout of ns_gemm64_kernel (lane l supplies A[l & 15][l >> 4],
+// B[l >> 4][l & 15]).  Chunks of 32 k go through LDS, the next one prefetched into registers.
 // KC = false: the sources run along x (a table: k = row, x = column) and a chunk is kept [k][x];
 // KC = true : they run along k (rows of L) and a chunk is kept [x][k].  load(which, x, k) returns the element (zero outside).
-template <bool KC, class Load>
-__device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, double* sA, double* sB, f64x4 (&acc)[2][2]) {
+// What a product adds to the chunk: fetch_more(kc) next to the prefetch of the chunk at kc, stash_more() next to its stores into LDS
+// (between the two barriers); what it does with the operands: step(k, a0, a1, b0, b1) per k-step of 4, k = this lane's k inside the
+// chunk, a0 / a1 and b0 / b1 the lane's operand elements of the wave's two row and two column blocks of 16.
+template <bool KC, class Load, class FetchMore, class StashMore, class Step>
+__device__ __forceinline__ void t64_tile_sweep(int k0, int k1, Load&& load, double* sA, double* sB, FetchMore&& fetch_more,
+                                               StashMore&& stash_more, Step&& step) {
   constexpr int kPer = kT64 * kT64K / kWThreads;  // 8 elements per thread, chunk and operand
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int l16 = lane & 15, kq = lane >> 4, ri = (w >> 1) * 32, rj = (w & 1) * 32;
@@ -112,6 +117,7 @@ __device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, do
       pa[e] = load(0, x, kc + k);
       pb[e] = load(1, x, kc + k);
     }
+    fetch_more(kc);
   };
   auto stash = [&]() {
 #pragma unroll
@@ -122,6 +128,7 @@ __device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, do
       sA[at] = pa[e];
       sB[at] = pb[e];
     }
+    stash_more();
   };
   if (k0 < k1) fetch(k0);
   for (int kc = k0; kc < k1; kc += kT64K) {
@@ -136,12 +143,51 @@ __device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, do
       const double a1 = KC ? sA[(ri + 16 + l16) * kT64Ldk + k] : sA[k * kT64Ld + ri + 16 + l16];
       const double b0 = KC ? sB[(rj + l16) * kT64Ldk + k] : sB[k * kT64Ld + rj + l16];
       const double b1 = KC ? sB[(rj + 16 + l16) * kT64Ldk + k] : sB[k * kT64Ld + rj + 16 + l16];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+      step(k, a0, a1, b0, b1);
     }
   }
+}
+
+// acc += sum_k A(x, k) B(y, k) over k0 <= k < k1 on one 64 x 64 tile, the accumulators as above
+template <bool KC, class Load>
+__device__ __forceinline__ void t64_tile_product(int k0, int k1, Load&& load, double* sA, double* sB, f64x4 (&acc)[2][2]) {
+  t64_tile_sweep<KC>(k0, k1, load, sA, sB, [](int) {}, [] {}, [&](int, double a0, double a1, double b0, double b1) {
+    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+  });
+}
+
+// acc[g] += sum_k w_g(k) A(x, k) B(y, k) over the rows 0 <= k < N of two blocks of 64 columns of a table, for G weightings of its rows at
+// once: ONE staged chunk of the two operands (KC = false) feeds G accumulator sets, the chunk's G x 32 weights staged next to it in sW
+// (G * kT64K doubles; thread t < 32 G stages weight(t / 32, k) of row k = t mod 32).  The weight goes into ONE operand fragment, in
+// registers (no square root: w a is exact for a 0 / 1 weight); weight(g, k) returns 0 outside the table and for a weighting that is not
+// there.  A weighting's sums do not depend on g or on its neighbours.  Each set costs 32 accumulator registers (pairwise_wide.h).
+template <int G, class Load, class Weight>
+__device__ __forceinline__ void t64_weighted_tile_products(int N, Load&& load, Weight&& weight, double* sA, double* sB, double* sW,
+                                                           f64x4 (&acc)[G][2][2]) {
+  static_assert(G * kT64K <= kWThreads, "one thread per staged weight");
+  const int tid = threadIdx.x;
+  double pw = 0.0;
+  t64_tile_sweep<false>(
+      0, N, load, sA, sB,
+      [&](int kc) {
+        if (tid < G * kT64K) pw = weight(tid / kT64K, kc + tid % kT64K);
+      },
+      [&] {
+        if (tid < G * kT64K) sW[tid] = pw;
+      },
+      [&](int k, double a0, double a1, double b0, double b1) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const double wk = sW[g * kT64K + k], wa0 = wk * a0, wa1 = wk * a1;
+          acc[g][0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa0, b0, acc[g][0][0], 0, 0, 0);
+          acc[g][0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa0, b1, acc[g][0][1], 0, 0, 0);
+          acc[g][1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa1, b0, acc[g][1][0], 0, 0, 0);
+          acc[g][1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa1, b1, acc[g][1][1], 0, 0, 0);
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- control block and views

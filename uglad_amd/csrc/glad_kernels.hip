@@ -45,6 +45,7 @@ namespace uglad {
 #include "assoc_wide.h"
 #include "rank_wide.h"
 #include "pairwise_wide.h"
+#include "wcov_wide.h"
 #include "after_wide.h"
 #include "score_wide.h"
 #include "sort_wide.h"

@@ -28,6 +28,11 @@
 //
 // No atomics, no ballot, every sum in a fixed order, every buffer belongs to one problem: results are bit-reproducible and independent of K and
 // of the problem's place in the batch.  One linear chain of launches, no host readback.
+//
+// Over the edge lists of K = R problems (uglad_edge_frequency: the selection frequencies of stability selection; at the end of this file):
+//   gw_frequency_kernel         one thread per listed edge: count[i][j], count[j][i] += 1, and positive[..] where the weight is > 0 -- the
+//                               file's only atomics, on integers, whose sums do not depend on their order
+//   gw_frequency_totals_kernel  one workgroup: sum_{i < j} c_ij and sum_{i < j} c_ij (R - c_ij) in 64-bit integers
 #pragma once
 #include "sort_wide.h"
 
@@ -286,6 +291,48 @@ __global__ __launch_bounds__(kWThreads) void gw_finish_kernel(const int* __restr
     o[4] = s_sum[3] / n;
     o[5] = s_sum[2] == 0.0 ? 0.0 : s_sum[2] / s_sum[1];
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- edge frequencies
+// uglad_edge_frequency: how often every edge comes back over the R edge lists gw_edges_kernel leaves for K = R problems (the selection
+// frequencies of stability selection).  grid (ceil(E / 256), R), one thread per listed edge: the first edge_count[r] rows of list r, the
+// rest of a list is undefined and never read.  count[i][j] and count[j][i] += 1, positive[..] += 1 where the weight is > 0, on planes the
+// entry point has zeroed.  Integer atomics: the sums do not depend on their order.  An index outside the plane is skipped, not stored.
+__global__ __launch_bounds__(kWThreads) void gw_frequency_kernel(const int* __restrict__ edge_count, const int* __restrict__ edge_ij,
+                                                                 const float* __restrict__ edge_w, int E, int D, int* __restrict__ count,
+                                                                 int* __restrict__ positive) {
+  const int r = blockIdx.y, e = blockIdx.x * kWThreads + threadIdx.x;
+  if (e >= E || e >= edge_count[r]) return;
+  const size_t at = (size_t)r * E + e;
+  const int i = edge_ij[2 * at], j = edge_ij[2 * at + 1];
+  if (i < 0 || j < 0 || i >= D || j >= D || i == j) return;
+  atomicAdd(count + (size_t)i * D + j, 1);
+  atomicAdd(count + (size_t)j * D + i, 1);
+  if (edge_w[at] > 0.f) {
+    atomicAdd(positive + (size_t)i * D + j, 1);
+    atomicAdd(positive + (size_t)j * D + i, 1);
+  }
+}
+
+// grid (1): totals = {sum_{i < j} c_ij, sum_{i < j} c_ij (R - c_ij)} in 64-bit integers -- row i's columns j > i strided over the threads,
+// the 256 partial sums combined by thread 0 (integers: any order gives the same bits).  StARS' instability is 2 totals[1] / (R^2 E).
+__global__ __launch_bounds__(kWThreads) void gw_frequency_totals_kernel(const int* __restrict__ count, int R, int D, long long* __restrict__ totals) {
+  __shared__ long long s_a[kWThreads], s_b[kWThreads];
+  const int tid = threadIdx.x;
+  long long a = 0, b = 0;
+  for (int i = 0; i < D; ++i)
+    for (int j = i + 1 + tid; j < D; j += kWThreads) {
+      const long long c = count[(size_t)i * D + j];
+      a += c;
+      b += c * ((long long)R - c);
+    }
+  s_a[tid] = a;
+  s_b[tid] = b;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 1; k < kWThreads; ++k) a += s_a[k], b += s_b[k];
+  totals[0] = a;
+  totals[1] = b;
 }
 
 }  // namespace uglad

@@ -246,6 +246,28 @@ int uglad_pairwise_covariance(const double* X, int K, int N, int D, int normaliz
   return launch_status();
 }
 
+int uglad_weighted_covariance_workspace_floats(int R, int D) { return wide_workspace_floats(R, D, 1, wcov_weighting_floats); }
+
+int uglad_weighted_covariance(const double* X, const double* W, int R, int N, int D, double eval_offset, float* S_out, double* S64_out,
+                              double* mean_out, int* info_out, double* min_eig_out, float* workspace, uglad_stream_t stream) {
+  if (!X || !W || !S_out || !info_out || !wide_workspace_ok(workspace)) return UGLAD_E_NULL;
+  if (uglad_weighted_covariance_workspace_floats(R, D) < 0 || N < 1) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const WcovView v = wcov_view(workspace, D);
+  const WcovOut out{S_out, S64_out, mean_out, info_out};
+  const int nt = v.c.DP / kT64, groups = (R + kWcovGroup - 1) / kWcovGroup;
+  const dim3 wg(kWThreads);
+  hipLaunchKernelGGL(covw_stats_kernel, dim3(nt, 1), wg, 0, st, X, N, D, 0, v.c);  // X as a single table: its column means, shared
+  hipLaunchKernelGGL(wcov_stats_kernel, dim3(nt, R), wg, 0, st, X, W, N, D, v, out);
+  hipLaunchKernelGGL(wcov_gram_kernel<kWcovGroup>, dim3(nt, nt, groups), wg, 0, st, X, W, R, N, D, v, out);
+  if (!min_eig_out) return launch_status();  // no repair
+  // as uglad_covariance_wide over K = R slabs; a flagged weighting (it holds NaN) is barred behind the controller's reset
+  launch_cholw_bisection<CovwBracket>(st, R, D, eval_offset, v.c, S_out, min_eig_out,
+                                      [&] { hipLaunchKernelGGL(wcov_bar_kernel, dim3(R), dim3(64), 0, st, 0, v, min_eig_out); });
+  hipLaunchKernelGGL(wcov_bar_kernel, dim3(R), dim3(64), 0, st, 1, v, min_eig_out);
+  return launch_status();
+}
+
 int uglad_conditional_mean_wide_workspace_floats(int K, int D) { return wide_workspace_floats(K, D, 1, afterw_problem_floats); }
 
 int uglad_conditional_mean_wide(const double* precision, const double* mean, const float* observed, const double* values,
@@ -353,6 +375,21 @@ int uglad_graph_wide(const float* values, int from_precision, const int* n_keep,
     hipLaunchKernelGGL(gw_rowsum_kernel, dim3((D + kWThreads - 1) / kWThreads, K), wg, 0, st, triangles2, v);
     hipLaunchKernelGGL(gw_finish_kernel, dim3(K), wg, 0, st, degree, triangles2, stats, v);
   }
+  return launch_status();
+}
+
+int uglad_edge_frequency(const int* edge_count, const int* edge_ij, const float* edge_w, int R, int D, int* count_out, int* positive_out,
+                         long long* totals_out, uglad_stream_t stream) {
+  if (!edge_count || !edge_ij || !edge_w || !count_out || !positive_out || !totals_out) return UGLAD_E_NULL;
+  if (R < 1 || R > 65535 || D < 2 || D > UGLAD_MAX_DIM) return UGLAD_E_DIM;
+  hipStream_t st = (hipStream_t)stream;
+  const int E = D * (D - 1) / 2;
+  int rc;
+  if ((rc = zero_floats(reinterpret_cast<float*>(count_out), (size_t)D * D, st))) return rc;  // (int32 zeros are float zeros)
+  if ((rc = zero_floats(reinterpret_cast<float*>(positive_out), (size_t)D * D, st))) return rc;
+  hipLaunchKernelGGL(gw_frequency_kernel, dim3((E + kWThreads - 1) / kWThreads, R), dim3(kWThreads), 0, st, edge_count, edge_ij, edge_w, E, D,
+                     count_out, positive_out);
+  hipLaunchKernelGGL(gw_frequency_totals_kernel, dim3(1), dim3(kWThreads), 0, st, (const int*)count_out, R, D, totals_out);
   return launch_status();
 }
 

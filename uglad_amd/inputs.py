@@ -1,7 +1,8 @@
 """How a table becomes the matrix the path runs on: the covariance (host fp64 like the reference's prepare_data.get_covariance, or under
 `device_covariance` the device front-ends uglad_covariance / uglad_covariance_wide), the association matrix of a mixed table
-(uglad_association), the rank correlations of the nonparanormal model (uglad_rank_correlation) and the pairwise-complete covariance of a
-table with missing entries (uglad_pairwise_covariance).  `uglad_amd.main` re-exports the public names."""
+(uglad_association), the rank correlations of the nonparanormal model (uglad_rank_correlation), the pairwise-complete covariance of a
+table with missing entries (uglad_pairwise_covariance) and the covariances of one table under many weightings of its rows -- its
+resamples -- (uglad_weighted_covariance).  `uglad_amd.main` re-exports the public names."""
 from __future__ import annotations
 
 import contextlib
@@ -170,3 +171,35 @@ def pairwise_covariance(X, normalize: bool = False, repair: bool = True, eval_of
     if single:
         return out.S[0], (None if mn is None else float(mn[0])), out.counts[0]
     return out.S, mn, out.counts
+
+
+def weight_flag_message(flag: int) -> str:
+    """What one weighting's flag word (uglad_weighted_covariance's info_out) says; "" when none is set."""
+    return "; ".join(why for bit, why in _lib.WEIGHT_FLAGS.items() if int(flag) & bit)
+
+
+def weighted_covariance(X, W, repair: bool = True, eval_offset: float = 0.1):
+    """The covariances of ONE table under R weightings of its rows, on the device (uglad_weighted_covariance, csrc/wcov_wide.h; additive:
+    what resampling needs -- prepare_data.resample_weights draws bootstrap multiplicities and 0 / 1 subsamples): per weighting
+    sum_n w_n (x_n - mu)(x_n - mu)^T / sum_n w_n about its own weighted mean mu, the table uploaded and staged once for all of them.  X
+    is an (N, D) array or DataFrame, taken as it is (normalise it first where the model wants that); W is (R, N).  Returns (S, min_eig,
+    mean): S the (R, D, D) fp32 matrices on the device, with `repair` each shifted like a covariance (min eig <= 1e-6: S += (eval_offset -
+    min eig) I); min_eig the (R,) float64 array of the smallest eigenvalues before the repair (+inf where none was needed; None without
+    `repair`); mean the (R, D) float64 device tensor of the weighted means.  A NaN or an infinity in X raises ValueError.  A weighting
+    with a negative, NaN or infinite weight, or whose weights sum to zero, is NaN throughout and not repaired; a RuntimeWarning names it."""
+    tables, single, _ = _stacked_tables(X, "weighted_covariance")
+    if not single:
+        raise ValueError("weighted_covariance takes one (N, D) table")
+    table = tables[0]
+    if not np.isfinite(table).all():
+        raise ValueError("weighted_covariance: the table holds NaN or infinity; impute or drop those rows first")
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[1] != table.shape[0]:
+        raise ValueError(f"weighted_covariance: weights of shape {W.shape} for a table of {table.shape[0]} rows; (R, N) expected")
+    out = _lib.get_lib().weighted_covariance(torch.from_numpy(table).to(_lib.device()), _to_dev(W, torch.float64), eval_offset=eval_offset,
+                                             repair=repair, want_mean=True)
+    for r, flag in enumerate(out.info.cpu().numpy()):
+        if flag:
+            warnings.warn(f"weighted_covariance: weighting {r} holds NaN and is not repaired: {weight_flag_message(flag)}",
+                          RuntimeWarning, stacklevel=2)
+    return out.S, (None if out.min_eig is None else out.min_eig.cpu().numpy()), out.mean

@@ -26,14 +26,14 @@ import torch
 from . import _lib
 from .after import (  # noqa: F401  (everything after the path: uglad_amd/after.py)
     GRAPH_STAT_KEYS, METRIC_KEYS, RecoveredGraph, SampleScores, _to_model_coordinates, compute_graph_statistics, compute_map_estimate,
-    conditional_gaussian_batch, conditional_gaussian_with_probabilities, device_report_metrics, get_partial_correlations,
+    conditional_gaussian_batch, conditional_gaussian_with_probabilities, device_report_metrics, edge_frequency, get_partial_correlations,
     graph_from_partial_correlations, recovered_graph, sample_scores)
 from .dist import Collective, get_collective
 from .glad import glad
 from .glad.glad_params import GladParams
 from .inputs import (  # noqa: F401  (how a table becomes the input matrix: uglad_amd/inputs.py)
     _covariance, _rank_tables, _stacked_tables, _to_dev, device_covariance, mixed_association, pairwise_covariance, pairwise_flag_message,
-    rank_correlation)
+    rank_correlation, weight_flag_message, weighted_covariance)
 from .utils import prepare_data
 from .utils.metrics import report_metrics_all  # noqa: F401  (host-side API parity; the drivers count on the device)
 
@@ -745,6 +745,69 @@ class uGLAD_GL(_Estimator):
         cond_max = regime.warn_if_outside("uGLAD_GL.fit_pairwise", None)
         return self._finish_fit(start, verbose, None if pred_theta is None else pred_theta[0], model_glad, cond_max, compare_theta,
                                 L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+
+    def fit_stability(self, X, n_resamples=50, scheme="subsample", fraction=0.5, sparsity=0.1, seed=0, true_theta=None, eval_offset=0.1,
+                      epochs=250, lr=0.002, INIT_DIAG=0, L=15, verbose=True, node_names=None, sqrt_mode=None):
+        """`fit` with a measure of how far to trust every edge (additive; the reference ends in one graph: the selection frequencies of
+        stability selection and the instability of StARS, as R's huge offers them): the table is processed and normalised as `fit` does,
+        `n_resamples` weightings of its rows are drawn (prepare_data.resample_weights: `scheme` "subsample" with `fraction` of the rows,
+        or "bootstrap"; seeded by `seed`), the all-ones weighting is placed in front, and ONE device call forms and repairs the R + 1
+        covariances from one upload of the table (uglad_weighted_covariance).  One shared model is trained on that batch, every matrix
+        with the loss against itself as in multitask mode; on one device only.  Sets precision_ (the all-ones member: the full table's),
+        precision_resamples_ (R, D, D), edge_frequency_ / edge_sign_frequency_ ((D, D) float64: the fraction of the resamples whose
+        graph at `sparsity` holds the edge, and holds it with a positive partial correlation; uglad_edge_frequency), instability_
+        (StARS: the mean over the edges of 2 f (1 - f)), resample_weights_ (R, N), resample_min_eig_ (R,), and covariance_, location_,
+        data_min_ / data_range_, node_names_, model_glad and cond_max_ as `fit` does; stable_edges(), predict, recovered_graph(),
+        scoring and save / load work afterwards."""
+        start = time()
+        if verbose:
+            print("Running uGLAD on resamples of the table")
+        if get_collective().world_size > 1:
+            raise ValueError("fit_stability is not sharded over ranks: run it in one process")
+        processed = prepare_data.process_table(X, NORM="min_max", VERBOSE=verbose)
+        data_min, data_range = prepare_data.kept_min_range(X, processed)
+        X = np.array(processed, dtype=np.float64)
+        N, D = X.shape
+        if not np.isfinite(X).all():
+            raise ValueError("fit_stability: the processed table holds NaN or infinity")
+        R = int(n_resamples)
+        weights = prepare_data.resample_weights(N, R, scheme=scheme, fraction=fraction, rng=seed)
+        out = _lib.get_lib().weighted_covariance(_to_dev(X, torch.float64), _to_dev(np.vstack([np.ones((1, N)), weights]), torch.float64),
+                                                 eval_offset=eval_offset, repair=True)
+        for r, flag in enumerate(out.info.cpu().numpy()):
+            if flag:
+                raise ValueError(f"fit_stability: weighting {r} has no covariance: {weight_flag_message(flag)}")
+        one = Collective()
+        with glad.regime_monitor() as regime:
+            pred_theta, model_glad = _train_sharded(out.S, one, R + 1, epochs, lr, INIT_DIAG, L, verbose, sqrt_mode)
+        pred_theta = pred_theta.detach()
+        compare_theta = None
+        if true_theta is not None:
+            compare_theta = device_report_metrics(_to_dev(np.asarray(true_theta).reshape(1, D, D)), pred_theta[:1])[0]
+            if verbose:
+                print(f"Comparison - {compare_theta}")
+        self.edge_frequency_, self.edge_sign_frequency_, self.instability_ = edge_frequency(pred_theta[1:].contiguous(), sparsity=sparsity)
+        self.precision_resamples_ = pred_theta[1:].cpu().numpy()
+        self.resample_weights_ = weights
+        self.resample_min_eig_ = out.min_eig[1:].cpu().numpy()
+        self.covariance_ = prepare_data.empirical_covariance(X)
+        self.location_ = X.mean(axis=0)
+        self.data_min_, self.data_range_ = data_min, data_range
+        self.node_names_ = list(node_names) if node_names is not None else [f"node_{i}" for i in range(D)]
+        cond_max = regime.warn_if_outside("uGLAD_GL.fit_stability", None)
+        return self._finish_fit(start, verbose, pred_theta[0], model_glad, cond_max, compare_theta,
+                                L=L, INIT_DIAG=INIT_DIAG, eval_offset=eval_offset, sqrt_mode=sqrt_mode)
+
+    def stable_edges(self, threshold: float = 0.8):
+        """The edges fit_stability saw in at least `threshold` of its resamples (and in one at least): a list of (i, j, frequency), i < j,
+        by frequency descending and then by index."""
+        if getattr(self, "edge_frequency_", None) is None:
+            raise ValueError("call fit_stability() first")
+        f = self.edge_frequency_
+        i, j = np.triu_indices(f.shape[0], 1)
+        keep = (f[i, j] >= threshold) & (f[i, j] > 0)
+        rows = sorted(zip((-f[i, j][keep]).tolist(), i[keep].tolist(), j[keep].tolist()))
+        return [(a, b, -nf) for nf, a, b in rows]
 
     def predict(self, X=None, S=None) -> np.ndarray:
         """Inference-only pass: the trained 42 parameters applied to new data (no_grad forward, the reference's

@@ -654,6 +654,51 @@ def pairwise_covariance_host(X, normalize: bool = False, min_pairs: int = 2):
     return cov, np.rint(n).astype(np.int64)
 
 
+# --------------------------------------------------------------------------- resamples of one table
+def weighted_covariance_host(X, W):
+    """The covariances of ONE (N, D) table under the (R, N) row weightings W, as uglad_weighted_covariance defines them
+    (include/uglad_hip.h, csrc/wcov_wide.h; additive), fp64 numpy: per weighting, with s = sum_n w_n and mu = sum_n w_n x_n / s,
+    S = sum_n w_n (x_n - mu)(x_n - mu)^T / s -- centred DIRECTLY at each mu, deliberately not the device's shifted form: the tests'
+    oracle and the probe's baseline.  Integer weights give empirical_covariance of the table with row n repeated w_n times.  Returns
+    (S (R, D, D) float64, exactly symmetric, mu (R, D)); a weighting that sums to zero or holds a NaN comes out NaN by the arithmetic."""
+    X = np.asarray(X, dtype=np.float64)
+    W = np.asarray(W, dtype=np.float64)
+    if X.ndim != 2 or W.ndim != 2 or W.shape[1] != X.shape[0]:
+        raise ValueError("weighted_covariance_host takes one (N, D) table and (R, N) weights")
+    R, D = W.shape[0], X.shape[1]
+    S, mean = np.empty((R, D, D)), np.empty((R, D))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for r, w in enumerate(W):
+            s = w.sum()
+            mean[r] = (w[:, None] * X).sum(axis=0) / s
+            Z = X - mean[r]
+            cov = (Z * w[:, None]).T @ Z / s
+            S[r] = np.triu(cov) + np.triu(cov, 1).T  # (the mirror is a copy, as on the device)
+    return S, mean
+
+
+def resample_weights(N: int, n_resamples: int, scheme: str = "subsample", fraction: float = 0.5, rng=None) -> np.ndarray:
+    """(n_resamples, N) float64 row weights of `n_resamples` resamples of a table of N rows, integer-valued: "bootstrap" the
+    multiplicities of N draws with replacement (every row sums to N); "subsample" 0 / 1 with floor(fraction N) ones, drawn without
+    replacement (the subsampling of stability selection and StARS).  Seeded through `rng` (a seed or a Generator)."""
+    rng = _rng(rng)
+    if N < 1 or n_resamples < 1:
+        raise ValueError(f"resample_weights: N = {N} rows, {n_resamples} resamples")
+    W = np.zeros((n_resamples, N), dtype=np.float64)
+    if scheme == "bootstrap":
+        for r in range(n_resamples):
+            W[r] = np.bincount(rng.integers(0, N, size=N), minlength=N)
+    elif scheme == "subsample":
+        m = int(np.floor(fraction * N))
+        if not 1 <= m <= N:
+            raise ValueError(f"resample_weights: fraction {fraction} keeps {m} of {N} rows")
+        for r in range(n_resamples):
+            W[r, rng.choice(N, size=m, replace=False)] = 1.0
+    else:
+        raise ValueError(f"resample_weights: scheme {scheme!r} is neither 'bootstrap' nor 'subsample'")
+    return W
+
+
 # --------------------------------------------------------------------------- bench inputs
 def synthetic_covariance_batch(
     num_tasks: int,
